@@ -28,6 +28,13 @@ Under ``torch.distributed.run`` (WORLD_SIZE set) each process is one rank.
 Without a visible GPU the ranks run a dry run on CPU (gloo): the launch, the
 partitioner and the per-rank totals, nothing matched, ``value`` null.
 
+A plain run (``--gpus N --steps S --warmup W``) does what the headline figure needs and no
+more: it builds the batch, warms up, times the S steps and prints the line (``roofline`` and
+``cpu_baseline`` null).  ``--full`` adds every other leg: the per-kernel timing pass and the
+roofline, the PCIe-inclusive and processor-batch figures, the carry stream, C4's hand-off leg
+and the CPU baseline with its parity check.  ``--dump-outputs DIR`` writes what the last timed
+step computed (the CSR a caller collects) as ``DIR/<name>.npy``.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -41,6 +48,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "kafkastreams-cep_amd"))
 
+DUMP_CAP_BYTES = 48 << 20   # --dump-outputs: the arrays' total size stays under this (sampled above it)
 PEAK_HBM_GBS = 8000.0   # MI355X spec (MI355X_MICROARCH.md, chip-level parameters)
 METRIC = "events/sec (whole node), 3-stage A->B->C over 1M keys; achieved HBM GB/s"
 
@@ -64,6 +72,14 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: kernel timing pass + roofline, "
+                         "PCIe-inclusive, processor batches, carry stream, C4 hand-off, CPU baseline + parity "
+                         "(the options below trim these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's matches (the collected CSR) as "
+                         "DIR/<name>.npy (float32/float64; a fixed seeded sample of the matches over "
+                         f"{DUMP_CAP_BYTES >> 20} MB)")
     ap.add_argument("--events", type=int, default=None, help="events per GPU (c2)")
     ap.add_argument("--keys", type=int, default=None, help="keys per GPU")
     ap.add_argument("--cpu-threads", type=int, default=None,
@@ -85,7 +101,10 @@ def parse(argv=None):
     ap.add_argument("--gather-matches", action="store_true",
                     help="N > 1: after the timed steps, gather every rank's matches to rank 0 (12 B/match) and "
                          "time it")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def gather_stats(stats, world: int):
@@ -219,10 +238,12 @@ def dry_run(args, world: int, rank: int):
                 "config": {"workload": C["desc"], "keys_per_gpu": K,
                            "parallelism": f"key-hash sharded x{world}" if world > 1 else "1 GPU",
                            "events_per_rank": [int(p[0]) for p in per], "keys_per_rank": [int(p[1]) for p in per]},
-                "roofline": None, "cpu_baseline": None,
+                "roofline": None, "cpu_baseline": None, "full": bool(args.full),
                 "dry_run": "no GPU visible: launch, partitioner and per-rank totals on CPU (gloo); nothing matched"}
         if shard_info is not None:
             line["config"]["shard"] = shard_info[1]
+        if args.dump_outputs:
+            print("bench.py: dry run, nothing matched: --dump-outputs writes nothing", file=sys.stderr)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -298,15 +319,17 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if sess.path in (N.PATH_STENCIL, N.PATH_CHAIN):
+    n_matches, csum = sess.checksum()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sess.collect(raise_on_error=False), n_matches, csum, rank, world)
+    if args.full and sess.path in (N.PATH_STENCIL, N.PATH_CHAIN):
         # one more pass per step under HIP events on the launch stream (cep_last_kernel_ms)
         sess.set_timing(True)
         for _ in range(args.steps):
             step()
             kernel_ms.append(sess.last_kernel_ms())
-    avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    avg_kernel_ms = sum(kernel_ms) / len(kernel_ms) if kernel_ms else None
 
-    n_matches, csum = sess.checksum()
     stats = torch.tensor([float(n), float(n_matches), elapsed], dtype=torch.float64, device=dev)
     tot_events, tot_matches, t_max = gather_stats(stats, world)
     exch = None
@@ -327,33 +350,13 @@ def main(argv=None):
                 exch["gathered_matches"] = int(len(merged["match_record"]))
 
     if rank == 0:
-        plain = (sess.path == N.PATH_STENCIL and pat.info.stencil_k <= 7
-                 and os.environ.get("KCEP_STENCIL_KEYED") != "1")
-        if sess.path in (N.PATH_STENCIL, N.PATH_CHAIN):
-            k = pat.info.stencil_k
-            algo_bytes = 8.0 * n + 4.0 * k * n_matches          # 8 B/event + 4k B/match
-            # the plain kernel writes one int per match (its first record); stencil_gather writes
-            # the k-int rows: the kernel's own algorithmic bytes are 8 B/event + 4 B/match
-            kernel_bytes = 8.0 * n + 4.0 * n_matches if plain else algo_bytes
-        else:
-            out = sess.collect(raise_on_error=False)
-            n_ent = len(out["ent_record"])
-            # 8 B/event in (key + i32 value); CSR out: 20 B/match + 12 B/entry
-            algo_bytes = 8.0 * n + 20.0 * n_matches + 12.0 * n_ent
-            kernel_bytes = algo_bytes
-        if sess.path in (N.PATH_STENCIL, N.PATH_CHAIN):
-            # the plain kernel runs strict fixed-length patterns of k <= 7 (C2); the keyed one chains (C5)
-            roof_ms, roof_kernel = avg_kernel_ms, "stencil_plain_kernel" if plain else "stencil_kernel"
-        else:
-            # these paths write their CSR in later launches (runs_write / nfa_compact), so the bytes
-            # are divided by the whole step's device time (HIP events around cep_push_batch)
-            roof_ms = sum(batch_ms) / len(batch_ms)
-            roof_kernel = "whole cep_push_batch (" + ("runs_sim + runs_emit" if sess.path == N.PATH_RUNS
-                                                       else "nfa kernel + compaction") + ")"
-        achieved = kernel_bytes / (roof_ms * 1e-3) / 1e9
         value = tot_events * args.steps / t_max
         build = N.lib().cep_version().decode().rsplit(" ", 1)[-1]
-        traffic, traffic_src = _pmc_traffic(args.config, n, build)
+        roofline = roof_ms = None
+        if sess.path in (N.PATH_GENERAL, N.PATH_RUNS):
+            roof_ms = sum(batch_ms) / len(batch_ms)
+        if args.full:
+            roofline, roof_ms = _roofline(args.config, sess, pat, n, n_matches, avg_kernel_ms, roof_ms, build)
         line = {
             "metric": METRIC if args.config == "c2" else f"events/sec (whole node), {C['desc']}",
             "value": value,
@@ -373,11 +376,9 @@ def main(argv=None):
                        "parallelism": f"key-hash sharded x{world}" if world > 1 else "1 GPU",
                        "kernels": "compiled for the pattern (hiprtc)" if sess.jit else "built-in",
                        "forced_path": args.force_path, "nfa_kernel": args.nfa_kernel},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                         "frac": achieved / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": roof_kernel, "kernel_ms": roof_ms, "algo_bytes_per_launch": kernel_bytes,
-                         "algo_bytes_per_step": algo_bytes},
+            "roofline": roofline,
             "cpu_baseline": None,
+            "full": bool(args.full),
             "checksum": f"{csum:016x}",
             "build": build,
         }
@@ -391,15 +392,15 @@ def main(argv=None):
             line["first_kernel"] = {"name": {N.PATH_GENERAL: gname,
                                              N.PATH_RUNS: "kcep_runs_sim" if sess.jit else "runs_sim"}[sess.path],
                                     "ms": avg_kernel_ms}
-        if sess.path == N.PATH_GENERAL:
+        if args.full and sess.path == N.PATH_GENERAL:
             line["config"]["live_run_hwm"] = sess.live_run_hwm()     # run-explosion high-water mark
             # keys the resident (uncapped) run handed back: they outgrew even the whole device pool
             erec, ecode = sess.batch_errors()
             line["config"]["keys_over_device_pool"] = int(sum(1 for c in ecode if c == N.E_RUN_CAPACITY))
-        if world == 1 and args.config == "c4" and args.handoff_cap > 0 and not force:
+        if args.full and world == 1 and args.config == "c4" and args.handoff_cap > 0 and not force:
             line["handoff"] = _handoff_leg(ir, key, cols[0], ts, K, C["per_key"], args.handoff_cap, stream)
             line["config"]["keys_on_cpu"] = line["handoff"]["keys_on_cpu"]
-        if world == 1 and sess.path in (N.PATH_STENCIL, N.PATH_CHAIN) and not args.no_host_input:
+        if args.full and world == 1 and sess.path in (N.PATH_STENCIL, N.PATH_CHAIN) and not args.no_host_input:
             line["pcie_inclusive"], host = _pcie_inclusive(sess, n, key, cols, stream, csum)
             # the processor's own batch sizes (CEPStream.query batch_size defaults to 1 << 16): host
             # batches over PCIe, each collected, through a carry session
@@ -420,15 +421,86 @@ def main(argv=None):
             line["processor_batches"] += [
                 _arrival_batches(pat, n, K, key, cols, ts, stream, n_matches, csum, value / world, per=b, pipelined=p)
                 for b in args.processor_batch for p in (False, True)]
-        if world == 1 and sess.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS) and args.carry_batches > 1:
+        if (args.full and world == 1 and sess.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS)
+                and args.carry_batches > 1):
             line["carry_stream"] = _carry_stream(pat, n, K, key, cols, stream, args.carry_batches, n_matches, csum,
                                                  value / world)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = _cpu_baseline(args.config, key, cols, ts, ir, args.cpu_threads, n_matches, csum,
                                                  sess, stream)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _roofline(cfg, sess, pat, n, n_matches, avg_kernel_ms, batch_ms, build):
+    """--full: achieved HBM GB/s of the dominant kernel against the MI355X peak -> (roofline, kernel ms)."""
+    from kcep import native as N
+    plain = (sess.path == N.PATH_STENCIL and pat.info.stencil_k <= 7
+             and os.environ.get("KCEP_STENCIL_KEYED") != "1")
+    if sess.path in (N.PATH_STENCIL, N.PATH_CHAIN):
+        k = pat.info.stencil_k
+        algo_bytes = 8.0 * n + 4.0 * k * n_matches          # SURVEY §8(d): 8 B/event + 4k B/match
+        # the plain kernel writes one int per match (its first record); stencil_gather writes
+        # the k-int rows: the kernel's own algorithmic bytes are 8 B/event + 4 B/match
+        kernel_bytes = 8.0 * n + 4.0 * n_matches if plain else algo_bytes
+        # the plain kernel runs strict fixed-length patterns of k <= 7 (C2); the keyed one chains (C5)
+        roof_ms, roof_kernel = avg_kernel_ms, "stencil_plain_kernel" if plain else "stencil_kernel"
+    else:
+        out = sess.collect(raise_on_error=False)
+        n_ent = len(out["ent_record"])
+        # 8 B/event in (key + i32 value); CSR out: 20 B/match + 12 B/entry
+        algo_bytes = 8.0 * n + 20.0 * n_matches + 12.0 * n_ent
+        kernel_bytes = algo_bytes
+        # these paths write their CSR in later launches (runs_write / nfa_compact), so the bytes
+        # are divided by the whole step's device time (HIP events around cep_push_batch)
+        roof_ms = batch_ms
+        roof_kernel = "whole cep_push_batch (" + ("runs_sim + runs_emit" if sess.path == N.PATH_RUNS
+                                                   else "nfa kernel + compaction") + ")"
+    achieved = kernel_bytes / (roof_ms * 1e-3) / 1e9
+    traffic, traffic_src = _pmc_traffic(cfg, n, build)
+    return {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+            "frac": achieved / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": roof_kernel, "kernel_ms": roof_ms, "algo_bytes_per_launch": kernel_bytes,
+            "algo_bytes_per_step": algo_bytes}, roof_ms
+
+
+def dump_outputs(d, out, n_matches, csum, rank=0, world=1):
+    """--dump-outputs: the last timed step's matches as a caller collects them (cep_collect's CSR), one
+    ``<name>.npy`` per array (``<name>.rank<r>.npy`` with several ranks).  Record positions and offsets
+    are written as float64 (exact below 2**53), key ids and name ids as float32 (exact below 2**24; float64
+    above).  ``summary`` holds the whole output's match count, entry count and the 64-bit order-independent
+    checksum (cep_checksum) as four 16-bit words, most significant first.  Over DUMP_CAP_BYTES the matches
+    are a fixed sample (numpy default_rng(0), ascending match index, ``sample_index``) with their entries;
+    ``ent_off`` then indexes the sampled entries."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    mrec, mkey, eoff = out["match_record"], out["match_key"], out["ent_off"]
+    ename, erec = out["ent_name"], out["ent_record"]
+    nm, ne = len(mrec), len(erec)
+
+    def small(a):
+        return a.astype(np.float32 if a.size == 0 or int(np.abs(a).max()) < (1 << 24) else np.float64)
+
+    per_match = 8 + 8 + 8 + 8 + (16.0 * ne / nm if nm else 0.0)     # upper bound: every array as float64
+    keep = int(DUMP_CAP_BYTES // per_match)
+    if nm > keep:
+        idx = np.sort(np.random.default_rng(0).choice(nm, size=keep, replace=False))
+        lens = eoff[idx + 1] - eoff[idx]
+        new_off = np.zeros(keep + 1, np.int64)
+        np.cumsum(lens, out=new_off[1:])
+        ent = np.repeat(eoff[idx] - new_off[:-1], lens) + np.arange(int(new_off[-1]))
+        mrec, mkey, eoff, ename, erec = mrec[idx], mkey[idx], new_off, ename[ent], erec[ent]
+    else:
+        idx = np.arange(nm)
+    arrays = {"match_record": mrec.astype(np.float64), "match_key": small(mkey), "ent_off": eoff.astype(np.float64),
+              "ent_name": small(ename), "ent_record": erec.astype(np.float64),
+              "sample_index": idx.astype(np.float64),
+              "summary": np.array([n_matches, ne] + [(csum >> s) & 0xFFFF for s in (48, 32, 16, 0)], np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
 
 
 def _pcie_inclusive(sess, n, key, cols, stream, csum, steps=3):

@@ -21,7 +21,13 @@
 #endif
 #include <stdint.h>
 
+#ifdef KCEP_JIT
+// hiprtc materialises the embedded headers under its own temporary directory by the names they are
+// included by: a name with ".." would land outside it, in a directory shared by every user of the host
+#include "kcep.h"
+#else
 #include "../../include/kcep.h"
+#endif
 #include "kcep_dev.h"
 
 namespace kcep {

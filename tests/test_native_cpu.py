@@ -131,6 +131,22 @@ def test_general_kernels_build():
         cp.build_kernels(N.PATH_GENERAL)
 
 
+def test_kernel_build_leaves_no_header_outside_the_compilers_directory(tmp_path, monkeypatch):
+    """hiprtc writes the embedded headers (jit.cpp) below a directory of its own under TMPDIR, by the names they
+    are included by, and removes that directory afterwards.  A name with ".." put kcep.h into TMPDIR/include,
+    which every user of the host shares: the second user's builds then failed.  The pattern's constants
+    are used nowhere else, so the build is not served from the process-wide module cache."""
+    tmp = tmp_path / "a" / "b"
+    tmp.mkdir(parents=True)
+    monkeypatch.setenv("TMPDIR", str(tmp))
+    pat = (QueryBuilder().select("x").where(Event.value() == 918273).then()
+           .select("y").where(Event.value() == 918274).build())
+    cp = N.CompiledPattern(pat.to_ir(Schema([("value", "i32")])))
+    assert cp.info.runs_ok
+    cp.build_kernels(N.PATH_RUNS)
+    assert list(tmp_path.rglob("kcep.h")) == []
+
+
 def test_runs_eligibility():
     """Deterministic strict patterns take the runs path (compile.cpp analyse_runs): C3's
     oneOrMore predicate and its successor's are complementary comparisons."""
