@@ -444,6 +444,7 @@ int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st) {
   StencilLaunch L{key, col, topic, b->n, s->prog.as<StencilProgram>(), SP.k, SP.coltype, SP.use_topic, SP.chain,
                   s->slots.as<int32_t>(), tc, tc + ntiles + 1, s->counter.as<int64_t>(), s->out.as<int32_t>(),
                   s->out_cap, s->total.as<int64_t>(), StencilCarry{}, !getenv_flag("KCEP_STENCIL_KEYED"), nullptr};
+  L.key_mode = getenv_flag("KCEP_STENCIL_SPARSE_KEYS") ? 1 : getenv_flag("KCEP_STENCIL_DENSE_KEYS") ? 2 : 0;
   if (s->carry) {                                // the keys' halos: read the previous, write the next
     // the batch's error flags: one of two words by the stamp's parity; the other one, cleared by this
     // batch's scan kernel, serves the next batch (no memset launch per batch)

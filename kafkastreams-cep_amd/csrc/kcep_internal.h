@@ -247,6 +247,10 @@ struct StencilLaunch {
   int plain;                      // plain stencil (no carry, no chain, k <= 7): the keyless kernel (KCEP_STENCIL_KEYED=1: off)
   unsigned long long* clear_flag; // carry: the next batch's error-flag word, zeroed by the scan kernel (or null)
   DeliverArgs deliver;            // carry sessions' CEP_BATCH_DELIVER batches
+  // the plain kernel without carry reads keys at its candidates only (stencil_kernel.h window_same_keys):
+  // 0 each wave chooses, 1 every wave gathers (KCEP_STENCIL_SPARSE_KEYS=1), 2 every wave loads all its
+  // keys (KCEP_STENCIL_DENSE_KEYS=1)
+  int key_mode = 0;
 };
 
 // compile.cpp

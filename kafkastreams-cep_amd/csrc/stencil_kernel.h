@@ -11,7 +11,9 @@
 // one match at record j iff the k consecutive same-key records j-k+1..j satisfy
 // P1..Pk (the traversal is final -> begin, one event per stage).
 //
-// HBM-bound integer streaming: 4 B key + 4/8 B value per record in, 4*k B per
+// HBM-bound integer streaming: 4/8 B value per record in (plus 4 B key per record for the keyed
+// and carry kernels; the plain kernel without carry reads keys only where the stage predicates
+// already hold over a whole window, window_same_keys below: ~0.3 B per record in C2), 4*k B per
 // match out, one pass, ordered output:
 //   * 256-thread workgroups each own a super-tile of ST_SUB x 4096 records;
 //     no workgroup ever waits on another (no dequeue atomic, no look-back: a
@@ -89,7 +91,7 @@ struct Chunk {
 };
 
 // q-th 16-B vector of thread tid at base + q * STRIDE + 4 * tid (STRIDE: 4 x the threads sharing a tile)
-template <class VT, bool TOPIC, int STRIDE = ST_THREADS * 4>
+template <class VT, bool TOPIC, int STRIDE = ST_THREADS * 4, bool KEYS = true>
 __device__ __forceinline__ void load_chunk(Chunk<VT, TOPIC>& c, const int32_t* __restrict__ key,
                                            const VT* __restrict__ val, const int32_t* __restrict__ topic,
                                            int64_t base, int64_t n, int tid) {
@@ -97,7 +99,7 @@ __device__ __forceinline__ void load_chunk(Chunk<VT, TOPIC>& c, const int32_t* _
   for (int q = 0; q < ST_EPT / 4; q++) {
     const int64_t g = base + q * STRIDE + tid * 4;
     if (g + 3 < n) {
-      c.k[q] = ld_nt4(key + g);
+      if constexpr (KEYS) c.k[q] = ld_nt4(key + g);
       if constexpr (sizeof(VT) == 4) {
         c.v[q].a = ld_nt4(val + g);
       } else {
@@ -109,7 +111,7 @@ __device__ __forceinline__ void load_chunk(Chunk<VT, TOPIC>& c, const int32_t* _
       // tail of the stream: clamped element loads; records >= n get an empty mask
       const int64_t g0 = g < n ? g : n - 1, g1 = g + 1 < n ? g + 1 : n - 1;
       const int64_t g2 = g + 2 < n ? g + 2 : n - 1, g3 = g + 3 < n ? g + 3 : n - 1;
-      c.k[q] = v4i{key[g0], key[g1], key[g2], key[g3]};
+      if constexpr (KEYS) c.k[q] = v4i{key[g0], key[g1], key[g2], key[g3]};
       if constexpr (sizeof(VT) == 4) {
         c.v[q].a = v4i{__builtin_bit_cast(int32_t, val[g0]), __builtin_bit_cast(int32_t, val[g1]),
                        __builtin_bit_cast(int32_t, val[g2]), __builtin_bit_cast(int32_t, val[g3])};
@@ -776,12 +778,12 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
 
 // load_chunk for a tile that lies wholly inside the batch (uniform branch): uniform tile base
 // pointers and 32-bit lane offsets, so every load is one saddr + voffset instruction
-template <class VT, bool TOPIC>
+template <class VT, bool TOPIC, bool KEYS = true>
 __device__ __forceinline__ void load_tile(Chunk<VT, TOPIC>& c, const int32_t* __restrict__ key,
                                           const VT* __restrict__ val, const int32_t* __restrict__ topic,
                                           int64_t base, int64_t n, int tid) {
   if (base + ST_TILE > n) {
-    load_chunk<VT, TOPIC>(c, key, val, topic, base, n, tid);
+    load_chunk<VT, TOPIC, ST_THREADS * 4, KEYS>(c, key, val, topic, base, n, tid);
     return;
   }
   const int32_t* kb = key + base;
@@ -790,7 +792,7 @@ __device__ __forceinline__ void load_tile(Chunk<VT, TOPIC>& c, const int32_t* __
 #pragma unroll
   for (int q = 0; q < ST_EPT / 4; q++) {
     const uint32_t o = uint32_t(q * (ST_THREADS * 4) + tid * 4);
-    c.k[q] = ld_nt4(kb + o);
+    if constexpr (KEYS) c.k[q] = ld_nt4(kb + o);
     if constexpr (sizeof(VT) == 4) {
       c.v[q].a = ld_nt4(vb + o);
     } else {
@@ -801,12 +803,85 @@ __device__ __forceinline__ void load_tile(Chunk<VT, TOPIC>& c, const int32_t* __
   }
 }
 
+// Keys at candidates only (the kernel without carry).  The stage predicates read the value column
+// alone, so the window test first runs on the stage bits: a thread's 16-bit candidate mask.  Only a
+// candidate's window needs keys, and each thread holding one reads them from global memory itself:
+// its own 16 keys (one 64-B piece, four 16-B loads) and, when a candidate's window reaches back
+// past its first record, the K-1 keys before.  Every adjacent pair of the window is compared, so
+// a batch that breaks the grouping contract gets the answer the all-keys kernel gave.
+//   sparse wave: only the lanes with a candidate load (the others' bits are never read);
+//   dense wave:  all 64 lanes load their 16 keys -- the wave's 1024 keys, whole lines -- and take
+//                the keys before their first record from the lane below (DPP), lane 0 from memory.
+// The choice is per wave and uniform (StencilLaunch::key_mode; adaptive: by the number of lanes
+// holding a candidate against ST_PLAIN_DENSE_LANES), costs no barrier, and skips the keys
+// altogether for a wave without candidates.  g0: batch index of the thread's first record.
+// Returns the same-key bits of the thread's 24-record window (bit p: window record p has the key
+// of p-1; window record 8 is the thread's first), valid where a candidate's window reads them.
+#ifndef ST_PLAIN_DENSE_LANES
+#define ST_PLAIN_DENSE_LANES 40                   // adaptive: a wave with more candidate lanes loads all its keys
+#endif
+// (the threshold by tools/stencil_sweep.py, profiles/stencil_sweep.md: adaptive within the spread of the better
+// forced mode at every candidate density; 16 and 28 lose 6 % at density 1/16, 52 equals 40.  C2: step 0.137 ->
+// 0.100 ms with the keys read this way; the next tile's values issued after barrier (A) instead: equal.)
+constexpr int ST_KEYS_ADAPTIVE = 0, ST_KEYS_SPARSE = 1, ST_KEYS_DENSE = 2;   // StencilLaunch::key_mode
+template <int K>
+__device__ __forceinline__ uint32_t window_same_keys(const int32_t* __restrict__ key, int64_t g0, int64_t n,
+                                                     uint32_t cand, int mode, int lane) {
+  const uint64_t holders = __ballot(cand != 0);
+  if (holders == 0) return 0;                     // uniform: no key of this wave's records is needed
+  const bool dense = mode == ST_KEYS_DENSE || (mode == ST_KEYS_ADAPTIVE && __popcll(holders) > ST_PLAIN_DENSE_LANES);
+  int32_t k[ST_EPT], pk[K - 1];
+#pragma unroll
+  for (int i = 0; i < ST_EPT; i++) k[i] = 0;
+#pragma unroll
+  for (int t = 0; t < K - 1; t++) pk[t] = 0;
+  auto own = [&](bool nt) {
+    if (g0 + ST_EPT <= n) {
+#pragma unroll
+      for (int q = 0; q < ST_EPT / 4; q++) {
+        const v4i v = nt ? ld_nt4(key + g0 + 4 * q) : *reinterpret_cast<const v4i*>(key + g0 + 4 * q);
+        k[4 * q] = v[0]; k[4 * q + 1] = v[1]; k[4 * q + 2] = v[2]; k[4 * q + 3] = v[3];
+      }
+    } else {                                      // the batch's tail: clamped (records >= n are no candidates)
+#pragma unroll
+      for (int i = 0; i < ST_EPT; i++) k[i] = key[g0 + i < n ? g0 + i : n - 1];
+    }
+  };
+  auto before = [&]() {                           // (a window that starts before record 0 is no candidate)
+#pragma unroll
+    for (int t = 0; t < K - 1; t++) {
+      const int64_t g = g0 - (K - 1) + t;
+      pk[t] = key[g < 0 ? 0 : g < n ? g : n - 1];
+    }
+  };
+  if (dense) {                                    // uniform
+    own(true);
+#pragma unroll
+    for (int t = 0; t < K - 1; t++)               // lane - 1's last K-1 keys (DPP wave_shr:1)
+      pk[t] = __builtin_amdgcn_update_dpp(0, k[ST_EPT - (K - 1) + t], 0x138, 0xF, 0xF, false);
+    if (lane == 0) before();
+  } else {
+    if (cand != 0) own(false);
+    if (cand & ((1u << (K - 1)) - 1u)) before();
+  }
+  uint32_t S = uint32_t(k[0] == pk[K - 2]) << 8;
+#pragma unroll
+  for (int i = 1; i < ST_EPT; i++) S |= uint32_t(k[i] == k[i - 1]) << (8 + i);
+#pragma unroll
+  for (int t = 1; t < K - 1; t++) S |= uint32_t(pk[t] == pk[t - 1]) << (8 - (K - 1) + t);
+  return S;
+}
+
 #ifndef ST_PLAIN_EARLY
-#define ST_PLAIN_EARLY 1                          // next tile's loads issued before the image barrier (A/B knob)
+#define ST_PLAIN_EARLY 1                         // next tile's loads issued before the image barrier (A/B knob)
 #endif
 #ifndef ST_PLAIN_WAVES
 #define ST_PLAIN_WAVES 6                          // waves per SIMD the register budget is cut for (A/B knob)
 #endif
+// (without the keys in the chunk the C2 kernel takes 71 VGPRs, 7 waves per SIMD, which 20.4 KB of LDS also allow.
+// Cut to 64 VGPRs with the staging buffer at 3968 matches, for 8 waves: C2 step equal within 1 %, all-candidate
+// batches 0.85 against 0.76 ms -- their tiles of ~4010 matches no longer fit the staging; and K >= 4 or a topic
+// column spill at 64.  profiles/stencil_sweep.md)
 // Carry sessions (CARRY): the same window test finds the records with K-1 same-key records before
 // them in the batch; the boundary records (the segment's first K-1) and the segments' ends are
 // visited as in stencil_kernel<CARRY> (halo reads, claims, halo writes), with their keys from a
@@ -831,12 +906,14 @@ template <int K, class VT, bool TOPIC, int SUB, bool CARRY>
 __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES) void stencil_plain_kernel(
     const int32_t* __restrict__ key, const VT* __restrict__ val, const int32_t* __restrict__ topic, int64_t n,
     const StencilProgram* __restrict__ P, int32_t* __restrict__ out, int64_t* __restrict__ tile_count,
-    int64_t ntiles, StencilCarry C) {
+    int64_t ntiles, StencilCarry C, int key_mode) {
   static_assert(K >= 1 && K <= 7, "bit 7 of a record's byte is its same-key bit");
   __shared__ __attribute__((aligned(16))) uint8_t s_mask[ST_TILE + 16];   // record r at r + 16
   __shared__ int32_t s_bk[CARRY ? ST_TILE + 16 : 1];   // carry: keys of segment starts/ends, record r at r + 16
-  __shared__ int32_t s_lastk[2][17];   // [tile & 1][m]: key of tile record 256m - 1 (m >= 1); [0][0]: before tile 0
-  __shared__ int32_t s_firstk[16];     // key of tile record 256m
+  // (the key tables, like bit 7 and the keys in the chunk, serve the carry variant only: without
+  // carry the keys are read at the candidates, window_same_keys)
+  __shared__ int32_t s_lastk[CARRY ? 2 : 1][CARRY ? 17 : 1];   // [tile & 1][m]: key of tile record 256m - 1 (m >= 1); [0][0]: before tile 0
+  __shared__ int32_t s_firstk[CARRY ? 16 : 1];     // key of tile record 256m
   __shared__ int32_t s_wsum[2][ST_THREADS / 64];
   __shared__ uint8_t s_tab[64];
   __shared__ uint8_t s_lut[256];
@@ -853,24 +930,27 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   const int ntl = int(ntiles - tile0 < SUB ? ntiles - tile0 : SUB);
 
   Chunk<VT, TOPIC> cur;
-  load_tile<VT, TOPIC>(cur, key, val, topic, tile0 * ST_TILE, n, tid);
+  load_tile<VT, TOPIC, CARRY>(cur, key, val, topic, tile0 * ST_TILE, n, tid);
   // the first tile's halo (its K-1 records before; later tiles take the previous tile's LDS bytes)
   const bool halo_lane = tid >= 16 - (K - 1) && tid < 16;
   const int64_t hg = tile0 * ST_TILE - 16 + tid;
   int32_t h_key = INT32_MIN, h_prev = INT32_MIN, h_top = 0;
   VT h_val{};
   if (halo_lane && hg >= 0) {
-    h_key = key[hg];
     h_val = val[hg];
     if constexpr (TOPIC) h_top = topic[hg];
-    if (hg > 0) h_prev = key[hg - 1];
+    if constexpr (CARRY) {
+      h_key = key[hg];
+      if (hg > 0) h_prev = key[hg - 1];
+    }
   }
   int32_t before0 = INT32_MIN;                    // key of the record before the workgroup's first tile
-  if (tid == 0 && tile0 > 0) before0 = key[tile0 * ST_TILE - 1];
+  if constexpr (CARRY)
+    if (tid == 0 && tile0 > 0) before0 = key[tile0 * ST_TILE - 1];
   __syncthreads();                                // the tables
   uint32_t h_mask = 0;
   if (halo_lane && hg >= 0)
-    h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top) | (uint32_t(hg > 0 && h_prev == h_key) << 7);
+    h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top) | (uint32_t(CARRY && hg > 0 && h_prev == h_key) << 7);
   int32_t h_bk = h_key;                           // carry: the history records' keys
   bool twice = false;                             // carry: a key claimed twice in this batch
 
@@ -893,18 +973,18 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
 #pragma unroll
     for (int q = 0; q < ST_EPT / 4; q++) {
       const int local = q * (ST_THREADS * 4) + tid * 4;
-      const v4i k = cur.k[q];
-      // the record before this lane's first: lane - 1's last (DPP wave_shr:1; lane 0: resolved by readers)
-      const int32_t kp = __builtin_amdgcn_update_dpp(INT32_MIN, k[3], 0x138, 0xF, 0xF, false);
-      const uint32_t same = uint32_t(lane > 0 && kp == k[0]) | (uint32_t(k[1] == k[0]) << 8) |
-                            (uint32_t(k[2] == k[1]) << 16) | (uint32_t(k[3] == k[2]) << 24);
-      uint32_t w = packed[q] | (same << 7);
+      uint32_t w = packed[q];
       const int64_t left = n - (base + local);    // records >= n match nothing
-      if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
-      *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
-      if (lane == 0) s_firstk[4 * q + wid] = k[0];
-      if (lane == 63) s_lastk[j & 1][4 * q + wid + 1] = k[3];
-      if constexpr (CARRY) {                      // the keys a visit may read (see above)
+      if constexpr (CARRY) {
+        const v4i k = cur.k[q];
+        // the record before this lane's first: lane - 1's last (DPP wave_shr:1; lane 0: resolved by readers)
+        const int32_t kp = __builtin_amdgcn_update_dpp(INT32_MIN, k[3], 0x138, 0xF, 0xF, false);
+        const uint32_t same = uint32_t(lane > 0 && kp == k[0]) | (uint32_t(k[1] == k[0]) << 8) |
+                              (uint32_t(k[2] == k[1]) << 16) | (uint32_t(k[3] == k[2]) << 24);
+        w |= same << 7;
+        if (lane == 0) s_firstk[4 * q + wid] = k[0];
+        if (lane == 63) s_lastk[j & 1][4 * q + wid + 1] = k[3];
+        // the keys a visit may read (see above)
         const int32_t kn = __builtin_amdgcn_update_dpp(INT32_MIN, k[0], 0x130, 0xF, 0xF, false);   // wave_shl:1
         // c_e: record e differs from the one before, or lies past the batch end (unloaded key)
         const bool c1 = k[1] != k[0] || left <= 1, c2 = k[2] != k[1] || left <= 2, c3 = k[3] != k[2] || left <= 3;
@@ -913,19 +993,22 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
         if (c2 || c3) s_bk[16 + local + 2] = k[2];
         if (c3 || lane == 63 || kn != k[3] || left <= 4) s_bk[16 + local + 3] = k[3];
       }
+      if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
+      *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
     }
     if (tid < 16) s_mask[tid] = halo_lane ? uint8_t(h_mask) : 0;
     if constexpr (CARRY)
       if (tid < 16) s_bk[tid] = h_bk;
-    if (j == 0 && tid == 0) s_lastk[0][0] = before0;
+    if constexpr (CARRY)
+      if (j == 0 && tid == 0) s_lastk[0][0] = before0;
     // the chunk is consumed: the next tile's loads go out before the barrier, so a wave whose data
     // came early does not hold its refill back until the slowest wave's has arrived
 #if ST_PLAIN_EARLY
-    if (j + 1 < ntl) load_tile<VT, TOPIC>(cur, key, val, topic, base + ST_TILE, n, tid);
+    if (j + 1 < ntl) load_tile<VT, TOPIC, CARRY>(cur, key, val, topic, base + ST_TILE, n, tid);
 #endif
     __syncthreads();                              // (A) the tile's image
 #if !ST_PLAIN_EARLY
-    if (j + 1 < ntl) load_tile<VT, TOPIC>(cur, key, val, topic, base + ST_TILE, n, tid);   // prefetch
+    if (j + 1 < ntl) load_tile<VT, TOPIC, CARRY>(cur, key, val, topic, base + ST_TILE, n, tid);   // prefetch
 #endif
 
     const int lb = ST_EPT * tid + 8;              // LDS byte of window record 0 (tile record 16 tid - 8)
@@ -933,15 +1016,17 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
 #pragma unroll
     for (int q = 0; q < 3; q++) m8[q] = *reinterpret_cast<const uint64_t*>(&s_mask[lb + 8 * q]);
     uint32_t S = 0;
+    if constexpr (CARRY) {
 #pragma unroll
-    for (int q = 0; q < 3; q++) S |= byte_bits(m8[q], 7) << (8 * q);
-    // the window's record at a multiple of 256 (if any): its same-key bit from the key tables
-    const int rb = ((ST_EPT * tid + 15) >> 8) << 8;
-    const int pb = rb - (ST_EPT * tid - 8);
-    if (pb >= 0 && pb < 24) {
-      const int m = rb >> 8;
-      const int32_t kb = m == 0 ? (j == 0 ? s_lastk[0][0] : s_lastk[(j - 1) & 1][16]) : s_lastk[j & 1][m];
-      S = (S & ~(1u << pb)) | (uint32_t(kb == s_firstk[m]) << pb);
+      for (int q = 0; q < 3; q++) S |= byte_bits(m8[q], 7) << (8 * q);
+      // the window's record at a multiple of 256 (if any): its same-key bit from the key tables
+      const int rb = ((ST_EPT * tid + 15) >> 8) << 8;
+      const int pb = rb - (ST_EPT * tid - 8);
+      if (pb >= 0 && pb < 24) {
+        const int m = rb >> 8;
+        const int32_t kb = m == 0 ? (j == 0 ? s_lastk[0][0] : s_lastk[(j - 1) & 1][16]) : s_lastk[j & 1][m];
+        S = (S & ~(1u << pb)) | (uint32_t(kb == s_firstk[m]) << pb);
+      }
     }
     uint32_t h = 0xFFFFFFFFu;
     uint32_t Bs[K];
@@ -953,6 +1038,9 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
       Bs[s] = B;
       h &= B << (K - 1 - s);
     }
+    // without carry: h holds the candidates (own records: bits 8..23); their keys decide
+    if constexpr (!CARRY && K > 1)
+      S = window_same_keys<K>(key, base + ST_EPT * tid, n, (h >> 8) & 0xFFFFu, key_mode, lane);
 #pragma unroll
     for (int d = 0; d < K - 1; d++) h &= S << d;
     uint32_t hit = (h >> 8) & 0xFFFFu;
@@ -1161,11 +1249,11 @@ inline void launch_kts(const StencilLaunch& L, int64_t ntiles, hipStream_t st) {
       if (L.carry.hdr)
         hipLaunchKernelGGL((stencil_plain_kernel<K, VT, TP, SUB, true>), dim3(unsigned(nsuper)), dim3(ST_THREADS), 0, st,
                            L.key, static_cast<const VT*>(L.val), L.topic, L.n, L.prog_dev, L.slots, L.tile_count,
-                           ntiles, L.carry);
+                           ntiles, L.carry, L.key_mode);
       else
         hipLaunchKernelGGL((stencil_plain_kernel<K, VT, TP, SUB, false>), dim3(unsigned(nsuper)), dim3(ST_THREADS), 0, st,
                            L.key, static_cast<const VT*>(L.val), L.topic, L.n, L.prog_dev, L.slots, L.tile_count,
-                           ntiles, L.carry);
+                           ntiles, L.carry, L.key_mode);
       return;
     }
   }
