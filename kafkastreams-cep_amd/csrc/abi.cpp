@@ -445,6 +445,10 @@ int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st) {
                   s->slots.as<int32_t>(), tc, tc + ntiles + 1, s->counter.as<int64_t>(), s->out.as<int32_t>(),
                   s->out_cap, s->total.as<int64_t>(), StencilCarry{}, !getenv_flag("KCEP_STENCIL_KEYED"), nullptr};
   L.key_mode = getenv_flag("KCEP_STENCIL_SPARSE_KEYS") ? 1 : getenv_flag("KCEP_STENCIL_DENSE_KEYS") ? 2 : 0;
+  // the 16-bit super-tile counts: the tile_pre region from its first 16-B boundary on (2 B per super-tile
+  // where tile_pre has 8 B per tile: it fits from one tile up)
+  L.tile_count16 = reinterpret_cast<uint16_t*>((reinterpret_cast<uintptr_t>(L.tile_pre) + 15) & ~uintptr_t(15));
+  L.split_finish = getenv_flag("KCEP_STENCIL_SPLIT_FINISH");
   if (s->carry) {                                // the keys' halos: read the previous, write the next
     // the batch's error flags: one of two words by the stamp's parity; the other one, cleared by this
     // batch's scan kernel, serves the next batch (no memset launch per batch)

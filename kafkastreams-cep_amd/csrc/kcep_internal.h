@@ -251,6 +251,11 @@ struct StencilLaunch {
   // 0 each wave chooses, 1 every wave gathers (KCEP_STENCIL_SPARSE_KEYS=1), 2 every wave loads all its
   // keys (KCEP_STENCIL_DENSE_KEYS=1)
   int key_mode = 0;
+  // the plain kernel without carry also stores each super-tile's count as a 16-bit word (a super-tile holds
+  // at most 16384 matches): 16-B aligned, in the tile_pre region, which the one-launch finish
+  // (stencil.hip stencil_finish_dense) does not use
+  uint16_t* tile_count16 = nullptr;
+  int split_finish = 0;           // KCEP_STENCIL_SPLIT_FINISH=1: tile_scan + stencil_gather_dense instead of that launch
 };
 
 // compile.cpp

@@ -286,6 +286,125 @@ __global__ __launch_bounds__(1024) void stencil_finish_small(const int32_t* __re
   }
 }
 
+// The plain kernel's dense slots, SMALL_FINISH < nsuper <= 8192 super-tiles (the headline path): the scan
+// and the gather in one launch, with no workgroup waiting on another.  A workgroup owns FIN_G consecutive
+// super-tiles, FIN_WPS waves each, and sums the counts of every super-tile before its first itself --
+// from the 16-bit counts the plain kernel stores (StencilLaunch::tile_count16: 2 B per super-tile, at most
+// 16 KB, so the re-reads are served by L1 and L2; the int64 counts did not fit L1) -- as 16-B vectors,
+// every thread at most FIN_ROUNDS of them.  All loads are issued before the first wait, at addresses that
+// are valid whatever the counts are: the count vectors clamped to the last whole one below nsuper (the up
+// to 7 counts after it: one 16-bit load per thread), the workgroup's own FIN_G counts (lanes 0..FIN_G-1 of
+// every wave), a wave's first FIN_B x 64 slot words of its super-tile's dense region (the session
+// allocates ST_DENSE ints per tile; words at or past the count are loaded and not used).  So a workgroup
+// takes one memory round trip before its first row store where tile_scan + stencil_gather_dense took
+// three (the scan's, then count and prefix, then the slot words).  A super-tile with more matches than
+// the first round holds takes the rest FIN_U loads at a time.
+#ifndef FIN_G
+#define FIN_G 4                                   // super-tiles per workgroup (A/B knob)
+#endif
+#ifndef FIN_WPS
+#define FIN_WPS 1                                 // waves per super-tile (A/B knob)
+#endif
+#ifndef FIN_B
+#define FIN_B 5                                   // slot words per lane in the first round (C2: 251 +- 16 matches per super-tile)
+#endif
+constexpr int FIN_U = 4;                          // loads in flight per lane after the first round
+constexpr int FIN_THREADS = FIN_G * FIN_WPS * 64;
+constexpr int FIN_MAX_SUPER = 8 * 1024;           // tile_scan's one-pass limit: the range this kernel serves
+constexpr int FIN_ROUNDS = (FIN_MAX_SUPER / 8 + FIN_THREADS - 1) / FIN_THREADS;
+static_assert(FIN_THREADS <= 1024 && FIN_B * 64 * FIN_WPS <= ST_DENSE, "the first round stays inside the dense region");
+static_assert(int64_t(FIN_MAX_SUPER) * ST_SUB * ST_TILE < (int64_t(1) << 31), "32-bit partial sums of the counts");
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+template <int K>
+__global__ __launch_bounds__(FIN_THREADS) void stencil_finish_dense(const int32_t* __restrict__ slots,
+                                                                    const uint16_t* __restrict__ cnt16,
+                                                                    int32_t* __restrict__ out, int64_t out_cap, int nsuper,
+                                                                    int sub, int64_t* __restrict__ total) {
+  __shared__ int32_t s_w[FIN_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int t0 = int(blockIdx.x) * FIN_G;          // the workgroup's first super-tile (< nsuper)
+  const int g = wid / FIN_WPS, part = wid % FIN_WPS;
+  const int t = t0 + g;                            // this wave's super-tile
+  const int tc = t < nsuper ? t : nsuper - 1;      // (a wave past the last super-tile loads that one's words, unused)
+  // (b) the first slot words
+  const int32_t* const dense = slots + int64_t(tc) * ST_DENSE;
+  int32_t v[FIN_B];
+#pragma unroll
+  for (int q = 0; q < FIN_B; q++) v[q] = dense[(q * FIN_WPS + part) * 64 + lane];
+  // (a) the counts: whole vectors of 8 (nfull >= 1: nsuper > SMALL_FINISH), the tail, the workgroup's own
+  const int nfull = nsuper >> 3;
+  v4u cv[FIN_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < FIN_ROUNDS; r++) {
+    const int i = r * FIN_THREADS + tid;
+    cv[r] = *reinterpret_cast<const v4u*>(cnt16 + 8 * (i < nfull ? i : nfull - 1));
+  }
+  const int ti = 8 * nfull + (tid & 7);
+  const int tail = cnt16[ti < nsuper ? ti : nsuper - 1];
+  const int oi = t0 + (lane < FIN_G ? lane : 0);
+  const int own = cnt16[oi < nsuper ? oi : nsuper - 1];
+  int before = 0;                                  // counts of the super-tiles before t0
+#pragma unroll
+  for (int r = 0; r < FIN_ROUNDS; r++) {
+    const int i = r * FIN_THREADS + tid;
+    const int nb = i < nfull ? t0 - 8 * i : 0;     // the vector's counts below t0: all 8, or the first nb
+    if (nb >= 8) {
+#pragma unroll
+      for (int w = 0; w < 4; w++) before += int(cv[r][w] & 0xFFFFu) + int(cv[r][w] >> 16);
+    } else if (nb > 0) {                           // the vector that holds t0 (one thread of the workgroup)
+#pragma unroll
+      for (int w = 0; w < 4; w++)
+        before += (2 * w < nb ? int(cv[r][w] & 0xFFFFu) : 0) + (2 * w + 1 < nb ? int(cv[r][w] >> 16) : 0);
+    }
+  }
+  if (tid < 8 && ti < t0) before += tail;          // (ti < t0 < nsuper)
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d, 64);
+  if (lane == 0) s_w[wid] = before;
+  __syncthreads();
+  int64_t p = 0;                                   // matches before this wave's super-tile
+#pragma unroll
+  for (int w = 0; w < FIN_THREADS / 64; w++) p += s_w[w];
+  int c = 0, csum = 0;
+#pragma unroll
+  for (int i = 0; i < FIN_G; i++) {
+    const int ci = t0 + i < nsuper ? __builtin_amdgcn_readlane(own, i) : 0;
+    p += i < g ? ci : 0;
+    c = i == g ? ci : c;
+    csum += ci;
+  }
+  if (t0 + FIN_G >= nsuper && tid == 0) *total = p + csum;   // (d) the last super-tile's workgroup (g = 0): the total
+  // (c) rows
+  if (p + c > out_cap || c <= 0) return;           // (t >= nsuper: c = 0)
+  int32_t* const dst = out + p * K;
+#pragma unroll
+  for (int q = 0; q < FIN_B; q++) {
+    const int m = (q * FIN_WPS + part) * 64 + lane;
+    if (m < c) {
+#pragma unroll
+      for (int s = 0; s < K; s++) dst[int64_t(m) * K + s] = v[q] + s;
+    }
+  }
+  const int32_t* const over = slots + int64_t(nsuper) * ST_DENSE + int64_t(t) * sub * ST_TILE;
+  // denser data only: the rest FIN_U loads at a time (clamped to the last match), their rows after them
+  for (int m0 = FIN_B * FIN_WPS * 64; m0 < c; m0 += FIN_U * FIN_WPS * 64) {   // uniform
+    int32_t w[FIN_U];
+#pragma unroll
+    for (int u = 0; u < FIN_U; u++) {
+      const int m = m0 + (u * FIN_WPS + part) * 64 + lane, mm = m < c ? m : c - 1;
+      w[u] = (mm < ST_DENSE ? dense : over)[mm];
+    }
+#pragma unroll
+    for (int u = 0; u < FIN_U; u++) {
+      const int m = m0 + (u * FIN_WPS + part) * 64 + lane;
+      if (m < c) {
+#pragma unroll
+        for (int s = 0; s < K; s++) dst[int64_t(m) * K + s] = w[u] + s;
+      }
+    }
+  }
+}
+
 // The end of a delivered batch: the last workgroup to finish (a ticket in device memory) stamps the host
 // header, after every workgroup's writes were made visible to the host -- cep_collect spins on that word
 // instead of waiting for the stream (one wake-up latency fewer per flush).
@@ -538,7 +657,13 @@ hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k,
                                   const StencilCarry& C, const DeliverArgs& D, hipStream_t st);
 
 // stencil_kernel (timed as the dominant kernel between ev0 and ev1), then the
-// tile-count scan and the gather into the contiguous output
+// tile-count scan and the gather into the contiguous output.  By the number of super-tiles:
+//   <= SMALL_FINISH (1024)  one workgroup, scan and gather in one launch (stencil_finish_small, or for carry
+//                           flushes one of the stencil_finish_deliver kernels)
+//   <= 8192                 the plain kernel's dense slots: stencil_finish_dense, one launch (each workgroup
+//                           scans the 16-bit counts itself); every other slot format, or with
+//                           KCEP_STENCIL_SPLIT_FINISH=1: tile_scan + gather, two launches
+//   above                   exclusive_scan (multi-workgroup) + gather
 hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st) {
   // null events: timing off (cep_session_set_timing), no event packets in the stream
   const DeliverArgs& D = L.deliver;
@@ -577,6 +702,22 @@ hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1
   if (nsuper <= SMALL_FINISH) {
     hipLaunchKernelGGL(stencil_finish_small, dim3(1), dim3(1024), 0, st, L.slots, L.tile_count, nsuper, L.k, L.out,
                        L.out_cap, sub, L.total, L.clear_flag, F);
+  } else if (F.dense && nsuper <= FIN_MAX_SUPER && !L.split_finish) {
+    // the plain kernel without carry (no clear_flag), the range tile_scan served: scan and gather in one
+    // launch over the 16-bit counts (KCEP_STENCIL_SPLIT_FINISH=1: the two launches below)
+    decltype(&stencil_finish_dense<1>) f = nullptr;
+    switch (L.k) {
+      case 1: f = stencil_finish_dense<1>; break;
+      case 2: f = stencil_finish_dense<2>; break;
+      case 3: f = stencil_finish_dense<3>; break;
+      case 4: f = stencil_finish_dense<4>; break;
+      case 5: f = stencil_finish_dense<5>; break;
+      case 6: f = stencil_finish_dense<6>; break;
+      case 7: f = stencil_finish_dense<7>; break;
+      default: return hipErrorInvalidValue;       // (the plain kernel: k <= 7)
+    }
+    hipLaunchKernelGGL(f, dim3(unsigned((nsuper + FIN_G - 1) / FIN_G)), dim3(FIN_THREADS), 0, st, L.slots,
+                       L.tile_count16, L.out, L.out_cap, int(nsuper), sub, L.total);
   } else {
     if (nsuper <= 8 * 1024) {
       hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, L.tile_count, nsuper, L.tile_pre, L.total, L.clear_flag);

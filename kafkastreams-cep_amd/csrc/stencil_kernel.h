@@ -29,6 +29,10 @@
 //   * then an exclusive scan of those counts and stencil_gather move the
 //     slots into one contiguous output in record order (matches are sparse:
 //     ~2% of records in C2, so this touches ~2 x 18 MB against 800 MB read).
+//     The plain kernel without carry also stores each super-tile's count as a
+//     16-bit word; for 1025..8192 super-tiles (C2: 6104) one launch does both,
+//     stencil.hip stencil_finish_dense: every workgroup sums the 16-bit counts
+//     before its super-tiles itself and writes their rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -906,8 +910,9 @@ template <int K, class VT, bool TOPIC, int SUB, bool CARRY>
 __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES) void stencil_plain_kernel(
     const int32_t* __restrict__ key, const VT* __restrict__ val, const int32_t* __restrict__ topic, int64_t n,
     const StencilProgram* __restrict__ P, int32_t* __restrict__ out, int64_t* __restrict__ tile_count,
-    int64_t ntiles, StencilCarry C, int key_mode) {
+    int64_t ntiles, StencilCarry C, int key_mode, uint16_t* __restrict__ tile_count16) {
   static_assert(K >= 1 && K <= 7, "bit 7 of a record's byte is its same-key bit");
+  static_assert(ST_SUB * ST_TILE <= 0xFFFF, "a super-tile's match count is also stored as a 16-bit word");
   __shared__ __attribute__((aligned(16))) uint8_t s_mask[ST_TILE + 16];   // record r at r + 16
   __shared__ int32_t s_bk[CARRY ? ST_TILE + 16 : 1];   // carry: keys of segment starts/ends, record r at r + 16
   // (the key tables, like bit 7 and the keys in the chunk, serve the carry variant only: without
@@ -1236,7 +1241,10 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
     return;
   }
 #endif
-  if (tid == 0) tile_count[blockIdx.x] = sum;
+  if (tid == 0) {
+    tile_count[blockIdx.x] = sum;
+    if constexpr (!CARRY) tile_count16[blockIdx.x] = uint16_t(sum);   // for stencil_finish_dense (stencil.hip)
+  }
   if constexpr (CARRY)
     if (twice) atomicOr(C.flags, 2ull);           // a key in two segments of the batch
 }
@@ -1249,11 +1257,11 @@ inline void launch_kts(const StencilLaunch& L, int64_t ntiles, hipStream_t st) {
       if (L.carry.hdr)
         hipLaunchKernelGGL((stencil_plain_kernel<K, VT, TP, SUB, true>), dim3(unsigned(nsuper)), dim3(ST_THREADS), 0, st,
                            L.key, static_cast<const VT*>(L.val), L.topic, L.n, L.prog_dev, L.slots, L.tile_count,
-                           ntiles, L.carry, L.key_mode);
+                           ntiles, L.carry, L.key_mode, L.tile_count16);
       else
         hipLaunchKernelGGL((stencil_plain_kernel<K, VT, TP, SUB, false>), dim3(unsigned(nsuper)), dim3(ST_THREADS), 0, st,
                            L.key, static_cast<const VT*>(L.val), L.topic, L.n, L.prog_dev, L.slots, L.tile_count,
-                           ntiles, L.carry, L.key_mode);
+                           ntiles, L.carry, L.key_mode, L.tile_count16);
       return;
     }
   }

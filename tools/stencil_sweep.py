@@ -8,7 +8,7 @@ neither).  With --modes lib the flags are left alone: that is the row of an olde
 KCEP_LIB, which has one mode.  One JSON line per density and mode; the match counts of all lines at a
 density must agree (checked within the run, and comparable across runs by "matches").
 
-usage: python tools/stencil_sweep.py [--modes sparse,dense,adaptive | --modes lib] [--tag NAME]
+usage: python tools/stencil_sweep.py [--modes sparse,dense,adaptive | --modes lib] [--tag NAME] [--thresholds 0,25,100]
 """
 import argparse
 import json
@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--modes", default="sparse,dense,adaptive")
     ap.add_argument("--tag", default="new")
+    ap.add_argument("--thresholds", type=lambda x: [int(v) for v in x.split(",") if v], default=THRESHOLDS,
+                    help="the values of t to run (default: all eight)")
     args = ap.parse_args()
 
     import torch
@@ -46,7 +48,7 @@ def main():
     val = torch.randint(0, 100, (n,), device=dev, dtype=torch.int32, generator=g)
     build = N.lib().cep_version().decode().rsplit(" ", 1)[-1]
     sch = Schema([("value", "i32")])
-    for t in THRESHOLDS:
+    for t in args.thresholds:
         q = (QueryBuilder().select("a").where(Event.value() < t).then().select("b").where(Event.value() < t)
              .then().select("c").where(Event.value() < t).build())
         sess = N.Session(N.CompiledPattern(q.to_ir(sch)), n, mode=N.MODE_PROCESSOR)
