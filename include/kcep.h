@@ -148,6 +148,35 @@ typedef struct {
                                          matches in arrival order of their completing record -- per record in
                                          matchPattern's emission order: the order context.forward sends them
                                          (:148) -- with cep_batch_errors in ascending position.  No host sort */
+#define CEP_BATCH_STOP_AT_ERROR 8     /* general-path batches: stop the batch at its first exception, as the
+                                         reference fails its task at the first exception process() throws
+                                         (CEPProcessor.java:134-149) and evaluates nothing after it.  Let p* be
+                                         the smallest stream position at which any key of the batch raises a
+                                         reference exception: any per-key CEP_E_* except CEP_E_RUN_CAPACITY, which
+                                         hands a key back and fails no task.  Positions are the batch's own:
+                                         arrival positions with CEP_BATCH_ARRIVAL_ORDER (p* is then exactly where
+                                         process() throws), base + index otherwise.  If no key raises, the batch
+                                         behaves exactly as without the flag.  If one does:
+                                         - cep_collect returns exactly the matches whose emitting record has a
+                                           position < p*, in the order that kind of batch already has (a key
+                                           handed back with CEP_E_RUN_CAPACITY at q < p* contributes its matches
+                                           below q, as always).  The result does not depend on which keys had
+                                           run past p* when the exception became visible;
+                                         - cep_batch_errors lists (p*, code) and the CEP_E_RUN_CAPACITY hand-backs
+                                           at positions < p*; a failure or hand-back past p* never happened.
+                                           cep_matches.err / err_record follow the usual rule over that list;
+                                         - cep_device_match_count and cep_checksum agree with the trimmed CSR;
+                                         - on CEP_SESSION_CARRY sessions no key's carried state is committed
+                                           (cep_key_state, cep_state_export and cep_state_evict give what they
+                                           gave before the push), while cep_stream_position still advances by n:
+                                           the failed batch's positions stay used;
+                                         - a key stops evaluating at its first record past p* once it can see
+                                           p*, and a key segment that starts past p* is skipped whole
+                                           (cep_batch_stopped).
+                                         A push that would run on another path (a stencil, chain or runs
+                                         session taking a batch those paths accept: bounded work per record, no
+                                         runaway keys) fails with CEP_E_UNSUPPORTED before it touches the
+                                         session */
 
 /* One batch of records, struct-of-arrays, grouped by key (each key's records
  * contiguous and in arrival order; or in plain arrival order with CEP_BATCH_ARRIVAL_ORDER).  Replaces a sequence of
@@ -237,6 +266,11 @@ int cep_session_set_timing(cep_session* s, int on);
    Call with records = codes = NULL for the count.  (The runs path lists up to 2^20 failing runs per batch;
    past that it reports the batch's first exception only.) */
 int cep_batch_errors(const cep_session* s, int64_t* records, int32_t* codes, int64_t cap, int64_t* n);
+/* CEP_BATCH_STOP_AT_ERROR, after a general-path batch: how many key segments the early-out stopped or
+   skipped whole, and how many of their records were left unevaluated.  Both 0 when no key raised or the
+   flag was off.  Diagnostics -- they depend on when the exception became visible to each key; nothing else
+   in the batch's result does.  CEP_E_UNSUPPORTED after a batch of another path. */
+int cep_batch_stopped(const cep_session* s, int64_t* keys, int64_t* records);
 /* CEP_SESSION_PROFILE sessions, after a general-path batch: per key segment {key id, live-run
    high-water mark, run evaluations, kernel wall clock (100 MHz ticks), then shader clocks spent in
    NFA.evaluate / edge predicates / buffer put+branch / removePattern / matchConstruction /

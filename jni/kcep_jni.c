@@ -65,7 +65,8 @@ JNIEXPORT jlong JNICALL CLS(cepSessionOpen)(JNIEnv* env, jclass c, jlong pattern
 JNIEXPORT jint JNICALL CLS(cepSessionPath)(JNIEnv* env, jclass c, jlong session) { return cep_session_path(S(session)); }
 
 /* cols: int[] / long[] / double[] per column type (1 / 2 / 3); flags: cep_batch.flags
-   (CEP_BATCH_OFFSETS_MONOTONE once the caller applied the high-water mark itself) */
+   (CEP_BATCH_OFFSETS_MONOTONE once the caller applied the high-water mark itself; CEP_BATCH_STOP_AT_ERROR = 8
+   OR-ed in on a CEP_PATH_GENERAL session stops the batch at its first exception) */
 JNIEXPORT jint JNICALL CLS(cepPushBatch)(JNIEnv* env, jclass c, jlong session, jint n, jintArray key,
                                          jintArray topic, jintArray partition, jlongArray offset, jlongArray ts,
                                          jintArray col_types, jobjectArray cols, jint flags) {

@@ -41,7 +41,7 @@ hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k,
 
 hipError_t nfa_launch(const NfaArgs& A, hipStream_t st, hipFunction_t jf);
 hipError_t nfa_wave_launch(const NfaArgs& A, int64_t grid, hipStream_t st, const JitModule* j);
-int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j);
+int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j, bool stop);
 hipError_t nfa_segments(const int32_t* key, int64_t n, int64_t* flag, int64_t* idx, int64_t* seg_start, int64_t* nseg,
                         int64_t* tmp, hipStream_t st);
 hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
@@ -61,8 +61,9 @@ hipError_t nfa_compact_launch(int64_t nseg, const int64_t* nseg_dev, int64_t nm,
                               const int32_t* key, const int64_t* seg_start, const int64_t* res_out, const int64_t* res_ent,
                               const int64_t* moff, const int64_t* eoff, int64_t* match_record, int32_t* match_key,
                               int64_t* ent_off, int32_t* ent_name, int64_t* ent_record, hipStream_t st);
+hipError_t nfa_trim_launch(const NfaArgs& A, int64_t nseg, hipStream_t st);
 hipError_t carry_commit_launch(int64_t nseg, const int32_t* key, const int64_t* seg_start, const int64_t* res_carry,
-                               const int32_t* res_err, int64_t* ctab, hipStream_t st);
+                               const int32_t* res_err, int64_t* ctab, const unsigned long long* stop_at, hipStream_t st);
 hipError_t carry_keycheck_launch(int64_t max_seg, const int64_t* nseg, const int32_t* key, const int64_t* seg_start,
                                 int32_t max_keys, int32_t* stamp, int32_t batch_no, unsigned long long* flags,
                                 hipStream_t st);
@@ -207,6 +208,13 @@ struct cep_session {
                                 // there, without re-running, until kPoolQuiet batches in a row fit the estimate
   int pool_quiet = 0;
   int last_attempts = 0;        // general path: kernel attempts of the last batch (1 + pool regrowths)
+  // CEP_BATCH_STOP_AT_ERROR (cep_batch_stopped): key segments the last general batch's early-out stopped or
+  // skipped, and their records left unevaluated
+  int64_t stopped_keys = 0, stopped_records = 0;
+  // records of the stopped batches since the last committed one: their positions stay used (base), but a
+  // state export still names the position the committed state stands at -- it is byte for byte the
+  // checkpoint before them
+  int64_t stop_uncommitted = 0;
   int64_t nseg = 0, g_matches = 0, g_entries = 0;
   int64_t nseg_hint = 0;        // the last general batch's segment count (pool estimate of the next)
   // ---- carried per-key state (CEP_SESSION_CARRY): NFAStore equivalent ----
@@ -227,6 +235,8 @@ struct cep_session {
   std::shared_ptr<const JitModule> jit;    // runs path
   std::shared_ptr<const JitModule> jitg;   // general path (built at open, or at the first general batch)
   bool jitg_tried = false;
+  std::shared_ptr<const JitModule> jitg_stop;   // its CEP_BATCH_STOP_AT_ERROR build (at the first flagged batch)
+  bool jitg_stop_tried = false;
   int64_t live_hwm = 0;                    // general path: most live runs any key held in the last batch
   bool wave = false;                       // general path: one key per wave (nfa_wave.h) for this pattern
   DBuf wscratch;                           // the wave kernel's recycled per-workgroup workspace regions
@@ -874,6 +884,8 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   s->e_code.clear();
   s->g_matches = s->g_entries = 0;
   s->nseg = 0;
+  s->stopped_keys = s->stopped_records = 0;
+  const bool stop = (b->flags & CEP_BATCH_STOP_AT_ERROR) != 0;
   A.base = s->carry ? s->base : 0;
   A.pos = s->cur_pos;
   if (n == 0) {                                   // cep_device_match_count reads scal[3]: zero it
@@ -890,7 +902,7 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   // last batch's (a pool overflow re-runs the batch with a larger one, as always)
   const bool dev_count = s->wave && !s->carry && s->nseg_hint > 0 && n < (int64_t(1) << 31);
   const size_t nb = size_t(n / 1024 + 2) * 16;
-  if (s->seg.ensure(size_t(n + 1) * 8) || s->scan_tmp.ensure(nb) || s->scal.ensure(64) || s->ctl.ensure(64))
+  if (s->seg.ensure(size_t(n + 1) * 8) || s->scan_tmp.ensure(nb) || s->scal.ensure(64) || s->ctl.ensure(128))
     return fail(CEP_E_HIP, "allocation failed");
   int64_t* scal = s->scal.as<int64_t>();
   HIPCHECK(nfa_segments(A.key, n, nullptr, nullptr, s->seg.as<int64_t>(), scal, s->scan_tmp.as<int64_t>(), st));
@@ -947,6 +959,17 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   A.cpool_top = ctl + 1;
   A.flags = reinterpret_cast<int32_t*>(ctl + 2);
   A.err_any = ctl + 4;
+  // CEP_BATCH_STOP_AT_ERROR: ctl[6] the earliest exception (~position, 0 none), ctl[7..8] stopped segments / records
+  A.stop_at = stop ? ctl + 6 : nullptr;
+  const int nctl = stop ? 9 : 5;                   // ctl words the host reads back
+  bool stop_hit = false;                           // the batch raised with the flag on: it stops at p*
+  // the kernels' build with the early-out in it: compiled for the pattern at the session's first flagged
+  // batch (on failure the built-in interpreting one, as for every compiled kernel)
+  if (stop && s->jitg && !s->jitg_stop_tried) {
+    s->jitg_stop = jit_general(P, s->jit_why, s->opts.flags & CEP_SESSION_PROFILE, true);
+    s->jitg_stop_tried = true;
+  }
+  const JitModule* jm = stop ? s->jitg_stop.get() : s->jitg.get();
   // lane kernel: 64 key segments per wave (fewer diverge less but leave the chip emptier: C4 gained 5 %
   // at 8 per wave, light keys lost 2x, profiles/r01_s5_nfa_spread_*.log)
   A.wave_agg = (wave_stateful(D) ? 1 : 0) | (P.has_seq ? 2 : 0);
@@ -961,7 +984,7 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   if (s->wave) {
     const char* scr_env = getenv("KCEP_WAVE_SCRATCH");
     const int64_t scr_words = scr_env ? std::max<int64_t>(0, atoll(scr_env)) & ~int64_t(3) : int64_t(1) << 14;
-    wgrid = nfa_wave_grid(nseg, A.wave_agg != 0, s->jitg.get());
+    wgrid = nfa_wave_grid(nseg, A.wave_agg != 0, jm, stop);
     A.scratch_words = scr_words;
     if (scr_words > 0) {
       if (s->wscratch.ensure(size_t(wgrid * scr_words) * 4)) return fail(CEP_E_HIP, "allocation failed");
@@ -1010,14 +1033,17 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
     A.cpool_cap = s->carry ? s->cpool_words : 0;
     A.last_attempt = attempt >= kMaxRetry || pool_at_limit ? 1 : 0;   // then an overflowing key is handed back per key
     A.max_key_words = s->opts.max_key_words;
-    // ctl: pool top, carry-pool top, flags (2 words), err_any, next segment (a kernel, not a copy command)
-    HIPCHECK(set_words_launch(reinterpret_cast<int64_t*>(ctl), 6, 1, s->cpool_used, st));
+    // ctl: pool top, carry-pool top, flags (2 words), err_any, next segment, then the stop words (a kernel,
+    // not a copy command)
+    HIPCHECK(set_words_launch(reinterpret_cast<int64_t*>(ctl), stop ? 9 : 6, 1, s->cpool_used, st));
     if (!timed) HIPCHECK(hipEventRecord(s->ev0, st));
     A.seg_next = reinterpret_cast<int32_t*>(ctl + 5);
-    if (s->wave) HIPCHECK(nfa_wave_launch(A, wgrid, st, s->jitg.get()));
-    else HIPCHECK(nfa_launch(A, st, s->jitg ? s->jitg->nfa : nullptr));
+    if (s->wave) HIPCHECK(nfa_wave_launch(A, wgrid, st, jm));
+    else HIPCHECK(nfa_launch(A, st, jm ? jm->nfa : nullptr));
     if (!timed) HIPCHECK(hipEventRecord(s->ev1, st));
     timed = true;
+    // CEP_BATCH_STOP_AT_ERROR: the keys' counts cut to the matches before the earliest exception
+    if (stop) HIPCHECK(nfa_trim_launch(A, nseg, st));
     // the CSR's match / entry counts are scanned right away, so that one synchronisation reads them
     // with the pool flags (a retried attempt scans again)
     HIPCHECK(exclusive_scan_pair(s->r_matches.as<int64_t>(), s->r_words.as<int64_t>(), nseg, A.nseg_dev,
@@ -1035,14 +1061,17 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
     if (!s->h_res) HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&s->h_res), 128, hipHostMallocMapped | hipHostMallocCoherent));
     int64_t* h_res_dev = nullptr;
     HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_res_dev), s->h_res, 0));
-    HIPCHECK(gather_words_launch(reinterpret_cast<const int64_t*>(ctl), 5, scal, 5, h_res_dev, st));
+    HIPCHECK(gather_words_launch(reinterpret_cast<const int64_t*>(ctl), nctl, scal, 5, h_res_dev, st));
     HIPCHECK(hipStreamSynchronize(st));
     unsigned long long res[5];
     int64_t sc[5];                                 // [0] segments, [3] matches, [4] entries
     for (int q = 0; q < 5; q++) {
       res[q] = (unsigned long long)s->h_res[q];
-      sc[q] = s->h_res[5 + q];
+      sc[q] = s->h_res[nctl + q];
     }
+    stop_hit = stop && s->h_res[6] != 0;
+    s->stopped_keys = stop_hit ? s->h_res[7] : 0;
+    s->stopped_records = stop_hit ? s->h_res[8] : 0;
     tots[0] = sc[3];
     tots[1] = sc[4];
     if (dev_count && attempt == 0) {               // the exact count from here on
@@ -1055,7 +1084,7 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
     if (fl[2]) return fail(CEP_E_ARG, "carry sessions need key ids in [0, max_keys)");
     s->live_hwm = fl[3];
     if (!fl[0] && !fl[1]) {
-      if (s->carry) s->cpool_used = int64_t(res[1]);
+      if (s->carry && !stop_hit) s->cpool_used = int64_t(res[1]);   // (a stopped batch commits no state)
       break;
     }
     if ((attempt >= kMaxRetry || pool_at_limit) && fl[0])
@@ -1099,8 +1128,9 @@ int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   }
   if (s->carry) {                                  // NFAStore.put of every key of the batch
     HIPCHECK(carry_commit_launch(nseg, A.key, A.seg_start, s->r_carry.as<int64_t>(), s->r_err.as<int32_t>(),
-                                 s->ctab.as<int64_t>(), st));
+                                 s->ctab.as<int64_t>(), A.stop_at, st));
     s->base += n;
+    s->stop_uncommitted = stop_hit ? s->stop_uncommitted + n : 0;
   }
   HIPCHECK(hipEventRecord(s->eb1, st));
   if (grew) {                                      // the next batches start from the grown size
@@ -1399,6 +1429,14 @@ int cep_session_jit(const cep_session* s) {
 
 int cep_session_wave(const cep_session* s) { return s && s->path == CEP_PATH_GENERAL && s->wave ? 1 : 0; }
 
+int cep_batch_stopped(const cep_session* s, int64_t* keys, int64_t* records) {
+  if (!s || !keys || !records) return fail(CEP_E_ARG, "null argument");
+  if (s->last_path != CEP_PATH_GENERAL) return fail(CEP_E_UNSUPPORTED, "the last batch did not run on the general path");
+  *keys = s->stopped_keys;
+  *records = s->stopped_records;
+  return CEP_OK;
+}
+
 int cep_batch_attempts(const cep_session* s) { return s && s->last_path == CEP_PATH_GENERAL ? s->last_attempts : 0; }
 
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed) {
@@ -1552,6 +1590,19 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   if (b->n_cols != int32_t(P.coltypes.size())) return fail(CEP_E_ARG, "column count does not match the pattern schema");
   for (int c = 0; c < b->n_cols; c++)
     if (b->n > 0 && !b->cols[c]) return fail(CEP_E_ARG, "null value column");
+  // records the processor would drop (null key/value, re-delivered offsets)
+  // break contiguity: the stencil only takes batches without them
+  const bool stencil_batch = !b->valid && !(s->opts.mode == CEP_MODE_PROCESSOR && b->offset &&
+                                            !(b->flags & CEP_BATCH_OFFSETS_MONOTONE));
+  // (rejected before any session state changes: cep_batch_id and the last batch's CSR stand)
+  if ((b->flags & CEP_BATCH_ARRIVAL_ORDER) && !s->carry)
+    return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_ARRIVAL_ORDER needs a CEP_SESSION_CARRY session");
+  if ((b->flags & CEP_BATCH_STOP_AT_ERROR) && s->path != CEP_PATH_GENERAL && stencil_batch) {
+    static const char* const kPath[] = {"", "stencil", "", "chain", "runs"};
+    return fail(CEP_E_UNSUPPORTED, std::string("CEP_BATCH_STOP_AT_ERROR is for general-path batches: this batch runs on "
+                                               "the ") + kPath[s->path >= 1 && s->path <= 4 ? s->path : 0] +
+                                       " path (bounded work per record, no runaway keys)");
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIPCHECK(hipSetDevice(s->device));
   s->stream = st;
@@ -1562,10 +1613,6 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   s->e_rec.clear();
   s->e_code.clear();
   if (s->timing) HIPCHECK(hipEventRecord(s->eb0, st));
-  // records the processor would drop (null key/value, re-delivered offsets)
-  // break contiguity: the stencil only takes batches without them
-  const bool stencil_batch = !b->valid && !(s->opts.mode == CEP_MODE_PROCESSOR && b->offset &&
-                                            !(b->flags & CEP_BATCH_OFFSETS_MONOTONE));
   s->h2d_wait = false;
   s->delivered = false;
   s->zc_slot = -1;
@@ -1573,8 +1620,6 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   s->last_gpos = nullptr;
   int rc = CEP_OK;
   const bool arrival = (b->flags & CEP_BATCH_ARRIVAL_ORDER) && b->n > 0;
-  if ((b->flags & CEP_BATCH_ARRIVAL_ORDER) && !s->carry)
-    return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_ARRIVAL_ORDER needs a CEP_SESSION_CARRY session");
   cep_batch gb;
   const void* gcols[16] = {};
   const int64_t base0 = s->base;
@@ -2148,7 +2193,8 @@ int cep_state_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, 
   if (cap < bytes) return fail(CEP_E_ARG, "export buffer too small");
   uint8_t* p = static_cast<uint8_t*>(buf);
   const uint32_t ver = 1;
-  memcpy(p, &kStateMagic, 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &s->base, 8); memcpy(p + 16, &nkeys, 4);
+  const int64_t at_pos = s->base - s->stop_uncommitted;
+  memcpy(p, &kStateMagic, 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &at_pos, 8); memcpy(p + 16, &nkeys, 4);
   p += 20;
   for (size_t i = 0; i < tab.size(); i++) {
     if (tab[i] < 0) continue;
@@ -2224,6 +2270,7 @@ int cep_state_clear(cep_session* s) {
   HIPCHECK(hipSetDevice(s->device));
   if (s->stream) HIPCHECK(hipStreamSynchronize(s->stream));
   s->base = 0;
+  s->stop_uncommitted = 0;
   if (halo_session(s)) {
     HIPCHECK(hipMemset(s->halo.p, 0, size_t(s->opts.max_keys) * sizeof(HaloHdr)));
     HIPCHECK(hipMemset(s->hflags.p, 0, 16));       // both error-flag words (by stamp parity)
@@ -2276,10 +2323,11 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
   out.clear();
   offs[0] = 0;
   const uint32_t ver = 1;
+  const int64_t at_pos = s->base - s->stop_uncommitted;
   auto header = [&](uint32_t magic, int32_t nk) {
     const size_t at = out.size();
     out.resize(at + 20);
-    memcpy(&out[at], &magic, 4); memcpy(&out[at + 4], &ver, 4); memcpy(&out[at + 8], &s->base, 8);
+    memcpy(&out[at], &magic, 4); memcpy(&out[at + 4], &ver, 4); memcpy(&out[at + 8], &at_pos, 8);
     memcpy(&out[at + 16], &nk, 4);
   };
   if (halo_session(s)) {

@@ -428,7 +428,7 @@ std::shared_ptr<const JitModule> jit_runs(const Program& P, std::string& why) {
   return build(src, names, slots, 2, why);
 }
 
-std::string jit_source_general(const Program& P, std::string& why, bool phases) {
+std::string jit_source_general(const Program& P, std::string& why, bool phases, bool stop) {
   std::string o = phases ? "#define KCEP_PHASES 1\n#include \"interp.h\"\n" : "#include \"interp.h\"\n";
   if (!gen_program(P, o, why)) return "";
   // waves per SIMD the register budgets are cut for: the lane kernel 2; the wave kernel 3 (166 VGPRs, no
@@ -440,12 +440,13 @@ std::string jit_source_general(const Program& P, std::string& why, bool phases) 
   // waves); HBM bytes per launch 1024: 275 MB, 1536: 234, 1664: 232 (profiles/r05_c4_arena.txt)
   const int waves = 2, wave_occ = 3;
   const std::string agg = wave_stateful(P.dev) || P.has_seq ? "true" : "false";
+  const std::string stp = stop ? "true" : "false";   // the CEP_BATCH_STOP_AT_ERROR build (nfa_dev.h stop_before)
   o += "#include \"nfa_dev.h\"\n#include \"nfa_wave.h\"\nextern \"C\" __global__ __launch_bounds__(64) "
        "__attribute__((amdgpu_waves_per_eu(" + std::to_string(waves) + R"())) void kcep_nfa_kernel(kcep::NfaArgs A) {
-  kcep::nfa_kernel_body(A);
+  kcep::nfa_kernel_body<)" + stp + R"(>(A);
 }
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu()" + std::to_string(wave_occ) + R"())) void kcep_nfa_wave(kcep::NfaArgs A) {
-  kcep::nfa_wave_body<)" + agg + R"(>(A);
+  kcep::nfa_wave_body<)" + agg + ", " + stp + R"(>(A);
 }
 extern "C" __global__ __launch_bounds__(256) void kcep_nfa_order(kcep::NfaArgs A, uint8_t* bits) {
   kcep::nfa_order_bits_body(A, bits);
@@ -454,8 +455,8 @@ extern "C" __global__ __launch_bounds__(256) void kcep_nfa_order(kcep::NfaArgs A
   return o;
 }
 
-std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases) {
-  const std::string src = jit_source_general(P, why, phases);
+std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases, bool stop) {
+  const std::string src = jit_source_general(P, why, phases, stop);
   if (src.empty()) return nullptr;
   static const char* const names[] = {"kcep_nfa_kernel", "kcep_nfa_wave", "kcep_nfa_order"};
   static hipFunction_t JitModule::* const slots[] = {&JitModule::nfa, &JitModule::nfa_wave, &JitModule::nfa_order};

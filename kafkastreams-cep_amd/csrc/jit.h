@@ -33,9 +33,10 @@ std::shared_ptr<const JitModule> jit_runs(const Program& P, std::string& why);
 bool jit_check_runs(const Program& P, std::string& why);
 
 // the same for the general NFA path's kernel (nfa_dev.h)
-std::string jit_source_general(const Program& P, std::string& why, bool phases = false);
-// phases: the profiling build (KCEP_PHASES clocks, CEP_SESSION_PROFILE sessions)
-std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases = false);
+std::string jit_source_general(const Program& P, std::string& why, bool phases = false, bool stop = false);
+// phases: the profiling build (KCEP_PHASES clocks, CEP_SESSION_PROFILE sessions); stop: the kernels'
+// CEP_BATCH_STOP_AT_ERROR build, a module of its own that only flagged batches compile and launch
+std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases = false, bool stop = false);
 bool jit_check_general(const Program& P, std::string& why);
 
 }  // namespace kcep

@@ -167,6 +167,10 @@ struct NfaArgs {
   unsigned long long* err_any;    // set when any key reports an exception (the host reads res_err only then)
   const int64_t* pos;             // stream position of each batch record (CEP_BATCH_ARRIVAL_ORDER: base + its
                                   // arrival index); null: base + record index
+  // CEP_BATCH_STOP_AT_ERROR (null: off): [0] the attempt's earliest reference exception as ~position
+  // (0: none yet; published with atomicMax, so the smallest position wins), [1] key segments the
+  // early-out stopped or skipped, [2] their records left unevaluated
+  unsigned long long* stop_at;
 };
 // a batch record's stream position (emitted entries, carried events, exception records)
 __device__ __forceinline__ int64_t a_pos(const NfaArgs& A, int64_t g) { return A.pos ? A.pos[g] : A.base + g; }

@@ -50,15 +50,17 @@
 
 namespace kcep {
 
+// STOP: the CEP_BATCH_STOP_AT_ERROR build (launched exactly when A.stop_at is set)
+template <bool STOP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void nfa_kernel(NfaArgs A) {
-  nfa_kernel_body(A);
+  nfa_kernel_body<STOP>(A);
 }
 
 // one key per wave, one queued run per lane (nfa_wave.h); AGG: patterns with aggregates or
 // SequenceMatchers.  A persistent grid (nfa_wave_grid)
-template <bool AGG>
+template <bool AGG, bool STOP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void nfa_wave_kernel(NfaArgs A) {
-  nfa_wave_body<AGG>(A);
+  nfa_wave_body<AGG, STOP>(A);
 }
 
 // ---- segments, scans, output compaction, carry commit ----
@@ -236,7 +238,8 @@ __global__ void scan_final(ScanPair S, const int64_t* __restrict__ bsum) {
   }
 }
 
-// jf: the pattern's compiled nfa kernel (jit.cpp), nullptr for the built-in interpreting one.
+// jf: the pattern's compiled nfa kernel (jit.cpp; its STOP build when A.stop_at is set), nullptr for the
+// built-in interpreting one.
 // One wave per workgroup, A.spread key segments per wave.
 hipError_t nfa_launch(const NfaArgs& A, hipStream_t st, hipFunction_t jf) {
   if (A.nseg <= 0) return hipSuccess;
@@ -246,7 +249,8 @@ hipError_t nfa_launch(const NfaArgs& A, hipStream_t st, hipFunction_t jf) {
     void* args[] = {&a};
     return hipModuleLaunchKernel(jf, grid, 1, 1, 64, 1, 1, 0, st, args, nullptr);
   }
-  hipLaunchKernelGGL(nfa_kernel, dim3(grid), dim3(64), 0, st, A);
+  if (A.stop_at) hipLaunchKernelGGL(nfa_kernel<true>, dim3(grid), dim3(64), 0, st, A);
+  else hipLaunchKernelGGL(nfa_kernel<false>, dim3(grid), dim3(64), 0, st, A);
   return hipGetLastError();
 }
 
@@ -366,11 +370,13 @@ hipError_t nfa_order_launch(const NfaArgs& A, int64_t nseg, uint8_t* bits, unsig
 
 // The workgroups (one wave each) the wave kernel's persistent grid should have: as many as the chip
 // holds at once (occupancy x compute units), at most one per segment.
-int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j) {
+int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j, bool stop) {
   int per_cu = 0, cus = 0, dev = 0;
   hipError_t e = j ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, j->nfa_wave, 64, 0)
-                   : agg ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<true>, 64, 0)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<false>, 64, 0);
+                 : agg ? (stop ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<true, true>, 64, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<true, false>, 64, 0))
+                       : (stop ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<false, true>, 64, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<false, false>, 64, 0));
   if (e != hipSuccess || per_cu <= 0) per_cu = 12;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
       cus <= 0)
@@ -387,8 +393,11 @@ hipError_t nfa_wave_launch(const NfaArgs& A, int64_t grid, hipStream_t st, const
   NfaArgs a = A;
   void* args[] = {&a};
   if (j) return hipModuleLaunchKernel(j->nfa_wave, unsigned(grid), 1, 1, 64, 1, 1, 0, st, args, nullptr);
-  if (A.wave_agg) hipLaunchKernelGGL(nfa_wave_kernel<true>, dim3(unsigned(grid)), dim3(64), 0, st, A);
-  else hipLaunchKernelGGL(nfa_wave_kernel<false>, dim3(unsigned(grid)), dim3(64), 0, st, A);
+  const dim3 g{unsigned(grid)}, b{64};
+  if (A.wave_agg && A.stop_at) hipLaunchKernelGGL((nfa_wave_kernel<true, true>), g, b, 0, st, A);
+  else if (A.wave_agg) hipLaunchKernelGGL((nfa_wave_kernel<true, false>), g, b, 0, st, A);
+  else if (A.stop_at) hipLaunchKernelGGL((nfa_wave_kernel<false, true>), g, b, 0, st, A);
+  else hipLaunchKernelGGL((nfa_wave_kernel<false, false>), g, b, 0, st, A);
   return hipGetLastError();
 }
 
@@ -444,6 +453,50 @@ hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n
   return hipGetLastError();
 }
 
+// CEP_BATCH_STOP_AT_ERROR: the batch as the reference leaves it when its task fails at the earliest
+// exception, stream position p* (NfaArgs.stop_at, final once the NFA kernel is done).  One thread per
+// segment: its matches are cut to those emitted at positions < p* (a key's headers are in emission
+// order, positions non-decreasing: a binary search; the entries of the first dropped match start where
+// the kept ones end), and a failure or hand-back recorded past p* -- by a key that ran ahead before
+// p* was visible -- is cleared.  The scans and the compaction after it then see the same counts
+// whichever keys had run past p*.
+__global__ __launch_bounds__(256) void nfa_trim(int64_t nseg, const int64_t* __restrict__ nseg_dev,
+                                                const unsigned long long* __restrict__ stop_at,
+                                                int64_t* __restrict__ res_matches, int64_t* __restrict__ res_words,
+                                                const int64_t* __restrict__ res_out, int32_t* __restrict__ res_err,
+                                                int64_t* __restrict__ res_err_rec) {
+  const int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (s >= (nseg_dev && *nseg_dev < nseg ? *nseg_dev : nseg)) return;
+  const unsigned long long w = *stop_at;
+  if (!w) return;                                  // no key raised: the batch stands as it is
+  const int64_t pstar = int64_t(~w);
+  const int64_t nm = res_matches[s];
+  if (nm > 0 && res_out[s]) {
+    const int4* h = reinterpret_cast<const int4*>(uintptr_t(res_out[s]));
+    int64_t lo = 0, hi = nm;                       // the first match emitted at or after p*
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      const int4 x = h[mid];
+      const int64_t pos = int64_t(uint64_t(uint32_t(x.x)) | (uint64_t(uint32_t(x.y)) << 32));
+      if (pos < pstar) lo = mid + 1; else hi = mid;
+    }
+    if (lo < nm) {
+      res_words[s] = h[lo].w;
+      res_matches[s] = lo;
+    }
+  }
+  if (res_err[s] && res_err_rec[s] > pstar) {
+    res_err[s] = 0;
+    res_err_rec[s] = -1;
+  }
+}
+hipError_t nfa_trim_launch(const NfaArgs& A, int64_t nseg, hipStream_t st) {
+  if (nseg <= 0 || !A.stop_at) return hipSuccess;
+  hipLaunchKernelGGL(nfa_trim, dim3(unsigned((nseg + 255) / 256)), dim3(256), 0, st, nseg, A.nseg_dev, A.stop_at,
+                     A.res_matches, A.res_words, A.res_out, A.res_err, A.res_err_rec);
+  return hipGetLastError();
+}
+
 // The segments' matches into one CSR in segment (key) order: one thread per match and one per entry,
 // each finding its segment by a binary search over the segments' exclusive prefixes (moff / eoff, in
 // L2), so that a key with thousands of matches is copied as fast as one with a single match.  A key's
@@ -485,12 +538,13 @@ __global__ void nfa_compact_entries(int64_t nseg, const int64_t* __restrict__ ns
   ent_record[e] = cw64(x + 1);
 }
 // NFAStoreImpl.put of every key of the batch: the key's table entry points at its new blob
-// (keys whose processing raised keep their previous state, like the failed task)
+// (keys whose processing raised keep their previous state, like the failed task).  stop_at
+// (CEP_BATCH_STOP_AT_ERROR, else null): once any key raised, the whole batch commits nothing
 __global__ void carry_commit(int64_t nseg, const int32_t* __restrict__ key, const int64_t* __restrict__ seg_start,
                              const int64_t* __restrict__ res_carry, const int32_t* __restrict__ res_err,
-                             int64_t* __restrict__ ctab) {
+                             int64_t* __restrict__ ctab, const unsigned long long* __restrict__ stop_at) {
   const int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (s >= nseg || res_err[s] || res_carry[s] < 0) return;
+  if (s >= nseg || res_err[s] || res_carry[s] < 0 || (stop_at && *stop_at)) return;
   ctab[key[seg_start[s]]] = res_carry[s];
 }
 // Carry sessions need each key in one contiguous segment (the batch contract of kcep.h): a key
@@ -551,10 +605,10 @@ hipError_t nfa_compact_launch(int64_t nseg, const int64_t* nseg_dev, int64_t nm,
 }
 
 hipError_t carry_commit_launch(int64_t nseg, const int32_t* key, const int64_t* seg_start, const int64_t* res_carry,
-                               const int32_t* res_err, int64_t* ctab, hipStream_t st) {
+                               const int32_t* res_err, int64_t* ctab, const unsigned long long* stop_at, hipStream_t st) {
   if (nseg <= 0) return hipSuccess;
   hipLaunchKernelGGL(carry_commit, dim3(unsigned((nseg + 255) / 256)), dim3(256), 0, st, nseg, key, seg_start,
-                     res_carry, res_err, ctab);
+                     res_carry, res_err, ctab, stop_at);
   return hipGetLastError();
 }
 

@@ -21,6 +21,27 @@
 
 namespace kcep {
 
+// CEP_BATCH_STOP_AT_ERROR.  The kernels come in two builds, STOP false and true (a template parameter
+// down to here): batches without the flag run the build that has none of this in its record loop, not
+// even the test of a null pointer (C4 was 0.5 % slower with it); A.stop_at is set
+// exactly when the STOP build runs.
+// A key that raises a reference exception at stream position pos makes it visible to every other key
+// of the batch (device scope)
+__device__ __forceinline__ void stop_publish(const NfaArgs& A, int64_t pos) {
+  atomicMax(A.stop_at, ~static_cast<unsigned long long>(pos));
+}
+// true when an exception is already known at a position before pos: the record at pos is never
+// evaluated by the reference.  A relaxed device-scope load: neither hoisted out of the record loop
+// nor served from a line the wave read earlier.
+__device__ __forceinline__ bool stop_before(const NfaArgs& A, int64_t pos) {
+  const unsigned long long w = __hip_atomic_load(A.stop_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return w != 0 && pos > static_cast<int64_t>(~w);
+}
+// a key segment stopped (or skipped whole) with `left` of its records unevaluated
+__device__ __forceinline__ void stop_count(const NfaArgs& A, int64_t left) {
+  atomicAdd(A.stop_at + 1, 1ull);
+  atomicAdd(A.stop_at + 2, static_cast<unsigned long long>(left));
+}
 
 constexpr int32_t EPS_NONE = 0xFF;
 // PROCEED/SKIP_PROCEED recursion depth (checked by the compiler).  The per-pattern kernels size the
@@ -1296,6 +1317,7 @@ __device__ __forceinline__ int64_t export_state(Lane& l) {
 // used when they fit, the match output stays in the pool (the compaction reads it after the kernel).
 // Arrays that outgrow it are re-allocated like any other (generic pointers throughout): from the
 // wave's scratch region (ka, wave kernel) or the pool.
+template <bool STOP = false>
 __device__ __forceinline__ bool key_begin(Lane& l, const NfaArgs& A, int seg, int32_t* arena = nullptr,
                                          int64_t arena_words = 0, KeyAlloc* ka = nullptr) {
   l.A = &A;
@@ -1321,6 +1343,16 @@ __device__ __forceinline__ bool key_begin(Lane& l, const NfaArgs& A, int seg, in
   A.res_err[seg] = 0;
   A.res_err_rec[seg] = -1;
   if (A.carry) A.res_carry[seg] = -1;
+  // CEP_BATCH_STOP_AT_ERROR: a segment that begins past the batch's earliest exception is skipped
+  // whole -- no workspace, its zero results above are final
+  if (STOP && stop_before(A, a_pos(A, l.seg0))) {
+    stop_count(A, l.L);
+    if (A.profile) {
+      int64_t* pr = A.profile + NFA_PROFILE_W * int64_t(seg);
+      for (int i = 0; i < NFA_PROFILE_W; i++) pr[i] = 0;
+    }
+    return false;
+  }
   const int32_t* blob = nullptr;
   if (A.carry) {
     const int32_t k = A.key[l.seg0];
@@ -1381,6 +1413,7 @@ __device__ __forceinline__ bool key_begin(Lane& l, const NfaArgs& A, int seg, in
       if (l.err) {
         A.res_err_rec[seg] = a_pos(A, l.seg0);
         atomicOr(A.err_any, 1ull);
+        if (STOP && !l.overflow) stop_publish(A, a_pos(A, l.seg0));
       }
       return false;
     }
@@ -1420,9 +1453,13 @@ __device__ __forceinline__ bool record_hwm(Lane& l, int64_t g) {
 // Per-key results: carried state (NFAStoreImpl.put :144-147), profile, the capacity hand-off,
 // match counts.
 // prof (profiling wave kernels): the key's allocator with its phase clocks and allocation counts
+// left (CEP_BATCH_STOP_AT_ERROR): records the early-out left unevaluated (0: the key ran to its end);
+// a stopped key is no error, and its state is not exported (the batch commits none)
+template <bool STOP = false>
 __device__ __forceinline__ void key_end(Lane& l, const NfaArgs& A, int seg, int64_t err_rec, int32_t live_max,
-                                        int64_t evals, uint64_t t0, const KeyAlloc* prof = nullptr) {
-  if (A.carry && !l.err && !l.overflow) {
+                                        int64_t evals, uint64_t t0, const KeyAlloc* prof = nullptr, int64_t left = 0) {
+  if (STOP && left > 0) stop_count(A, left);
+  if (A.carry && !l.err && !l.overflow && !(STOP && left > 0)) {
     const int64_t at = export_state(l);
     if (at >= 0) A.res_carry[seg] = at;
   }
@@ -1471,12 +1508,13 @@ __device__ __forceinline__ void key_end(Lane& l, const NfaArgs& A, int seg, int6
 }
 
 // One lane runs one key segment (A.spread segments per wave).
+template <bool STOP = false>
 __device__ __forceinline__ void nfa_kernel_body(const NfaArgs& A) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int seg = (gid >> 6) * A.spread + (gid & 63);
   if ((gid & 63) >= A.spread || seg >= A.nseg) return;
   Lane l;
-  if (!key_begin(l, A, seg)) return;
+  if (!key_begin<STOP>(l, A, seg)) return;
   const auto& P = KCEP_PROG(l);
   const int ns = P.nslots;
   Frame fr[MAXD];
@@ -1488,9 +1526,11 @@ __device__ __forceinline__ void nfa_kernel_body(const NfaArgs& A) {
   int32_t live_max = l.qlen;                                         // live-run high-water mark of the key
   int64_t evals = 0;
   const uint64_t t0 = A.profile ? wall_clock64() : 0;
+  int64_t left = 0;                                                  // records the early-out skipped
   for (int i = 0; i < l.L && !l.err && !l.overflow; i++) {
     const int r = l.C + i;
     const int64_t g = l.seg0 + i;
+    if (STOP && stop_before(A, a_pos(A, g))) { left = l.L - i; break; }   // CEP_BATCH_STOP_AT_ERROR
     l.r = r;
     l.g = g;
     for (int s = 0; s < ns; s++) { int32_t* nd = node(l, s, r); nd[0] = 0; nd[1] = -1; nd[2] = -1; nd[3] = 0; }
@@ -1503,13 +1543,16 @@ __device__ __forceinline__ void nfa_kernel_body(const NfaArgs& A) {
     l.rec_etop = l.etop;
     l.rec_nmatch = l.nmatch;
     if (!step(l, fr)) {
-      if (l.err) err_rec = a_pos(A, g);
+      if (l.err) {
+        err_rec = a_pos(A, g);
+        if (STOP && !l.overflow) stop_publish(A, err_rec);
+      }
       break;
     }
     live_max = l.qlen > live_max ? l.qlen : live_max;
     if (proc && !record_hwm(l, g)) { l.overflow = 1; break; }
   }
-  key_end(l, A, seg, err_rec, live_max, evals, t0);
+  key_end<STOP>(l, A, seg, err_rec, live_max, evals, t0, nullptr, left);
 }
 
 }  // namespace kcep

@@ -489,9 +489,10 @@ __device__ __forceinline__ bool wave_round_conflict(const Lane& l, int32_t* conf
 // AGG: the pattern reads or writes aggregates / reads partial sequences (DevProgram, abi.cpp
 // wave_stateful): the round machinery for them (conflict checks, the sequential re-evaluation,
 // applying the logged aggregate writes) is compiled in only then.
+// STOP: the CEP_BATCH_STOP_AT_ERROR build (nfa_dev.h stop_before): the early-out at the batch's earliest exception.
 // One key (segment `seg`) on the GL lanes of group gp (w, s_arena, s_priv: the group's LDS; scr: the
 // wave's scratch region of A.scratch_words words, or nullptr).
-template <bool AGG, int GL>
+template <bool AGG, int GL, bool STOP>
 __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL>& gp, WaveShared<GL>& w,
                                          int32_t* s_arena, int arena_words, int32_t* s_priv, int32_t* scr) {
   const int lane = gp.gl;
@@ -505,7 +506,7 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
 #ifdef KCEP_PHASES
     for (int i = 0; i <= AK_N; i++) w.ka.kw[i] = 0;
 #endif
-    ok = key_begin(l, A, seg, s_arena, arena_words, &w.ka) ? 1 : 0;
+    ok = key_begin<STOP>(l, A, seg, s_arena, arena_words, &w.ka) ? 1 : 0;
     if (ok) {
       lane_to_ws(w, l);
       w.arena = s_arena;
@@ -565,9 +566,12 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
     l.log_cap = log0;
   }
   l.wtop = &w.heap_top;
+  int64_t left = 0;                                              // records the early-out skipped
   for (int i = 0; i < l.L && !w.err && !w.overflow; i++) {
     const int r = l.C + i;
     const int64_t g = l.seg0 + i;
+    // CEP_BATCH_STOP_AT_ERROR: lane 0 reads the batch's earliest exception, the group follows it
+    if (STOP && gp.bcast(lane == 0 && stop_before(A, a_pos(A, g)) ? 1 : 0)) { left = l.L - i; break; }
     l.r = r;
     l.g = g;
     KWP_MARK(t_rec);
@@ -750,7 +754,11 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
       wave_sync();
       KWP_ADD(10, t_pl2);
     }
-    if (w.err) { err_rec = a_pos(A, g); break; }
+    if (w.err) {
+      err_rec = a_pos(A, g);
+      if (STOP && lane == 0 && !w.overflow) stop_publish(A, err_rec);
+      break;
+    }
     if (w.overflow) break;
     KWP_MARK(t_end);
     // swap the queues; matchConstruction (:151-158); the high-water mark on lane 0
@@ -773,7 +781,11 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
     }
     wave_sync();
     KWP_ADD(8, t_end);
-    if (w.err) { err_rec = a_pos(A, g); break; }
+    if (w.err) {
+      err_rec = a_pos(A, g);
+      if (STOP && lane == 0 && !w.overflow) stop_publish(A, err_rec);
+      break;
+    }
     live_max = w.qlen > live_max ? w.qlen : live_max;
   }
   wave_sync();
@@ -781,7 +793,7 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
     ws_to_lane(l, w);
     l.pool_words = int64_t(w.ka.pool_words);
     l.wpool = nullptr;
-    key_end(l, A, seg, err_rec, live_max, evals, t0, &w.ka);
+    key_end<STOP>(l, A, seg, err_rec, live_max, evals, t0, &w.ka, left);
   }
 }
 
@@ -789,7 +801,7 @@ __device__ __forceinline__ void wave_key(const NfaArgs& A, int seg, const Grp<GL
 // to the waves the chip holds at once, or the segment count if smaller): each workgroup takes the next
 // segment from A.seg_next until none is left, and every key it takes works in the workgroup's own
 // scratch region (recycled, so L2-resident, instead of a fresh stretch of the pool per key).
-template <bool AGG>
+template <bool AGG, bool STOP = false>
 __device__ __forceinline__ void nfa_wave_body(const NfaArgs& A) {
   constexpr int ARENA = WAVE_ARENA & ~3;   // LDS words of the key's hot workspace
   __shared__ WaveShared<WAVE> ws;
@@ -804,7 +816,7 @@ __device__ __forceinline__ void nfa_wave_body(const NfaArgs& A) {
     seg = gp.bcast(seg);
     if (seg >= nseg) break;                        // every wave of the grid reaches this
     if (A.seg_order) seg = A.seg_order[seg];
-    wave_key<AGG, WAVE>(A, seg, gp, ws, s_arena, ARENA, s_priv, scr);
+    wave_key<AGG, WAVE, STOP>(A, seg, gp, ws, s_arena, ARENA, s_priv, scr);
     wave_sync();
   }
 }

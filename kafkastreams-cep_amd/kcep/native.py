@@ -28,6 +28,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 BATCH_OFFSETS_MONOTONE = 1
 BATCH_DELIVER = 2          # the push is collected at once: matches handed to pinned host memory by the device
 BATCH_ARRIVAL_ORDER = 4    # records in arrival order: grouped by key on the device, matches back in arrival order
+BATCH_STOP_AT_ERROR = 8    # general path: the batch stops at its earliest exception, as the reference's task does
 SESSION_CARRY = 1
 SESSION_INTERPRET = 2
 SESSION_PROFILE = 4
@@ -78,7 +79,7 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_key_profile", "cep_key_hash", "cep_key_shard", "cep_shard_plan", "cep_partition", "cep_gather",
            "cep_match_count_to", "cep_state_evict", "cep_state_import_keys", "cep_state_positions",
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
-           "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch"]
+           "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped"]
 
 _lib = None
 
@@ -136,6 +137,8 @@ def lib():
     L.cep_live_run_hwm.argtypes = [P, C.POINTER(C.c_int64)]
     L.cep_session_set_timing.argtypes = [P, C.c_int32]
     L.cep_batch_errors.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    if hasattr(L, "cep_batch_stopped"):     # (KCEP_LIB A/B runs may load an older build)
+        L.cep_batch_stopped.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -351,6 +354,14 @@ class Session:
         if n.value:
             check(lib().cep_batch_errors(self.h, rec.ctypes.data, code.ctypes.data, n.value, C.byref(n)))
         return rec, code
+
+    def batch_stopped(self):
+        """BATCH_STOP_AT_ERROR, after a general-path batch: (key segments the early-out stopped or skipped
+        whole, their records left unevaluated); (0, 0) when no key raised or the flag was off
+        (cep_batch_stopped).  Diagnostics: the two depend on timing, the batch's result does not."""
+        k, r = C.c_int64(), C.c_int64()
+        check(lib().cep_batch_stopped(self.h, C.byref(k), C.byref(r)))
+        return k.value, r.value
 
     def key_profile(self):
         """``profile=True`` sessions: int64 array [n_keys, 25] (cep_key_profile): key, live-run max, run

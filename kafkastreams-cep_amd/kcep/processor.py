@@ -103,7 +103,8 @@ class GpuCEPProcessor:
 
     def __init__(self, queryName: str, pattern: Union[Pattern, bytes], schema: Schema, decoder: ColumnDecoder,
                  batch_size: int = 1 << 16, max_keys: int = 1 << 20, device: int = 0,
-                 mode: int = N.MODE_PROCESSOR, prune_at: int = 1 << 20, max_key_words: int = 0):
+                 mode: int = N.MODE_PROCESSOR, prune_at: int = 1 << 20, max_key_words: int = 0,
+                 stop_at_error: bool = False):
         if decoder.schema is not schema and decoder.schema.columns != schema.columns:
             raise ValueError("decoder and pattern use different schemas")
         self.queryName = queryName.lower().replace("\\s+", "")
@@ -112,6 +113,10 @@ class GpuCEPProcessor:
         self.batch_size = int(batch_size)
         self.max_keys = int(max_keys)
         self.max_key_words = int(max_key_words)
+        # general-path sessions: the device stops a batch at its first exception (CEP_BATCH_STOP_AT_ERROR)
+        # instead of running every other key to its end for matches flush() then drops; what is
+        # forwarded and raised is the same either way
+        self.stop_at_error = bool(stop_at_error)
         self.device = device
         self.mode = mode
         ir = pattern if isinstance(pattern, (bytes, bytearray)) else pattern.to_ir(schema)
@@ -236,9 +241,12 @@ class GpuCEPProcessor:
         base = self.session.stream_position()
         for i, r in enumerate(sorted_recs):
             self._log[base + i] = r[6]
+        flags = self._flags | N.BATCH_DELIVER | N.BATCH_ARRIVAL_ORDER
+        if self.stop_at_error and self.session.path == N.PATH_GENERAL:
+            flags |= N.BATCH_STOP_AT_ERROR
         try:
             self.session.push(n, np.ascontiguousarray(self._kid[perm]), cols, topic=topic, partition=part, offset=off,
-                              ts=ts, flags=self._flags | N.BATCH_DELIVER | N.BATCH_ARRIVAL_ORDER)
+                              ts=ts, flags=flags)
             out = self.session.collect(raise_on_error=False)
         except N.CepError as e:                           # no state was committed for this batch:
             self._failed = e                              # the task fails, as the reference's does
@@ -293,6 +301,11 @@ class GpuCEPProcessor:
             matches = [m for m in matches if m[1] not in cap]
             errors = [e for e in errors if e[1] != 9]
             idx = np.flatnonzero(np.isin(self._kid, np.fromiter(cap, np.int32, len(cap))))
+            if self.stop_at_error and errors:
+                # the task fails at the first push's earliest exception: the reference never sees the
+                # records from there on, and the re-run, which has no exception of its own to stop at,
+                # must not evaluate them either
+                idx = idx[idx < min(errors)[0]]
             self.session.set_max_key_words(0)
             try:
                 m2, e2 = self._run(recs, idx)
