@@ -19,15 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kcep_internal.h"
+#include "launch.h"
 
 namespace kcep {
-
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
-hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n, const int64_t* n_dev, int64_t* out0,
-                               int64_t* out1, int64_t* total0, int64_t* total1, int64_t* tmp, hipStream_t st);
-
-static unsigned blocks256(int64_t n) { return unsigned((std::max<int64_t>(n, 1) + 255) / 256); }
 
 namespace {
 

@@ -42,7 +42,7 @@
 #include <algorithm>
 
 #include "../../include/kcep.h"
-#include "kcep_internal.h"
+#include "launch.h"
 #include "interp.h"
 #include "nfa_dev.h"
 #include "nfa_wave.h"

@@ -28,7 +28,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/kcep.h"
-#include "kcep_internal.h"
+#include "launch.h"
 #include "interp.h"
 #include "runs_dev.h"
 
@@ -661,8 +661,6 @@ __global__ void rc_gc_copy(int64_t* __restrict__ rtab, int64_t nkeys, const int6
 
 }  // namespace
 
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
-
 static unsigned runs_blocks(int64_t items, int32_t chunk) {
   const int64_t waves = (items + chunk - 1) / chunk;
   return unsigned((waves * 64 + RT - 1) / RT);
@@ -770,8 +768,6 @@ hipError_t runs_emit_launch(const RunsArgs& R, const int32_t* end_of, const int6
                      R.chunk, span, pre, W, match_record, match_key, ent_off, ent_name, ent_record);
   return hipGetLastError();
 }
-
-static unsigned blocks256(int64_t n) { return unsigned((std::max<int64_t>(n, 1) + 255) / 256); }
 
 // the extended batch of a runs carry session: every batch segment prefixed by its key's tail.
 // seg_flag / seg_idx / seg_start / nseg: nfa_segments of the batch; nmax >= segment count (the batch

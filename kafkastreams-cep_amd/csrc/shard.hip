@@ -28,10 +28,10 @@
 #include <vector>
 
 #include "../../include/kcep.h"
+#include "launch.h"   // exclusive_scan (nfa.hip)
 
 namespace kcep {
 int set_error(int code, const std::string& msg);   // abi.cpp: cep_last_error()
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
 
 constexpr int PT_THREADS = 256;
 constexpr int PT_PER = 16;                       // consecutive records per thread

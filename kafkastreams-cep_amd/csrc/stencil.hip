@@ -54,9 +54,9 @@ struct SlotFormat {
   }
   // match m of super-tile t (c matches), stage s
   __device__ __forceinline__ int32_t entry(const int32_t* slots, int64_t t, int64_t c, int64_t m, int s) const {
-    if (dense)                                   // the plain kernel without carry (kcep_internal.h ST_DENSE)
+    if (dense)                                   // the plain kernel without carry (launch.h ST_DENSE)
       return (m < ST_DENSE ? slots[t * ST_DENSE + m] : slots[nsuper * ST_DENSE + t * int64_t(sub) * ST_TILE + m]) + s;
-    if (kdense && c <= ST_DENSE_KEYED) {         // the keyed kernel without carry (kcep_internal.h)
+    if (kdense && c <= ST_DENSE_KEYED) {         // the keyed kernel without carry (launch.h)
       const int64_t i = t * ST_DENSE_KEYED + m;
       return stencil_row(slots[i], reinterpret_cast<const uint8_t*>(slots + nsuper * ST_DENSE_KEYED)[i], s, k, chain,
                          carry);
@@ -651,10 +651,6 @@ static hipError_t stencil_count(const StencilLaunch& L, hipStream_t st) {
   }
   return hipErrorInvalidValue;
 }
-
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
-hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k, const int64_t* total, int64_t out_cap,
-                                  const StencilCarry& C, const DeliverArgs& D, hipStream_t st);
 
 // stencil_kernel (timed as the dominant kernel between ev0 and ev1), then the
 // tile-count scan and the gather into the contiguous output.  By the number of super-tiles:

@@ -38,7 +38,7 @@
 
 #include <type_traits>
 
-#include "kcep_internal.h"
+#include "launch.h"
 
 namespace kcep {
 
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
   // carry: the stages taken from the halo) after the super-tile's SUB x 4096 ints; stencil_gather
   // writes the K-int rows (stencil_row)
   // without carry, a super-tile of at most ST_DENSE_KEYED matches writes them to the dense regions
-  // (kcep_internal.h; uniform per workgroup), a larger one to its own region after them
+  // (launch.h; uniform per workgroup), a larger one to its own region after them
   constexpr bool KD = !CARRY && ST_KEYED_DENSE;
   const int64_t nsup = gridDim.x;
   int64_t stot = 0;
@@ -965,7 +965,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   uint8_t* const aux = reinterpret_cast<uint8_t*>(slot + SUB * ST_TILE);   // carry: per match, after the ints
   int64_t sum = 0;
   int nbuf = 0;                                   // STAGE: the first nbuf matches are staged in s_out (uniform)
-  // STAGE: the slot layout of kcep_internal.h ST_DENSE (the first matches in the dense region)
+  // STAGE: the slot layout of launch.h ST_DENSE (the first matches in the dense region)
   int32_t* const dense = out + int64_t(blockIdx.x) * ST_DENSE;
   int32_t* const over = out + int64_t(gridDim.x) * ST_DENSE + tile0 * ST_TILE;
   for (int j = 0; j < ntl; j++) {                 // uniform
@@ -1176,7 +1176,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
     const int32_t b32 = int32_t(base) - (K - 1);  // record index < 2^31 (checked by the launcher)
     if constexpr (STAGE) {
       // the super-tile's matches are staged in LDS and stored once, as one run into the dense region
-      // (kcep_internal.h ST_DENSE): C2 kernel 139 -> 131 us; storing each tile's run into the
+      // (launch.h ST_DENSE): C2 kernel 139 -> 131 us; storing each tile's run into the
       // super-tile's own region (196 KB apart) cost 16 us over no stores at all, with or without the
       // LDS staging (profiles/r04_ab_stencil_stores.txt)
       // A tile whose matches no longer fit (over a quarter of the super-tile's records matching)
