@@ -114,10 +114,13 @@ typedef struct {
                                 batch -- bounded only by the 2^31 records of an extended batch, past which the push
                                 fails with CEP_E_RUN_CAPACITY; such patterns, e.g. an unbounded oneOrMore that keeps
                                 matching, are better carried on the general path: cep_opts.force_path =
-                                CEP_PATH_GENERAL).  Both then take
-                                batches without null records (valid) and with per-key increasing offsets
-                                (CEP_BATCH_OFFSETS_MONOTONE; the host applies the high-water-mark rule); every
-                                other pattern carries its full NFA state on the general path. */
+                                CEP_PATH_GENERAL).  Both evaluate only admitted records: a batch either
+                                comes without null records (valid) and with per-key increasing offsets
+                                (CEP_BATCH_OFFSETS_MONOTONE: the host has applied the high-water-mark rule), or
+                                it is pushed with CEP_BATCH_FILTER and the library applies the null and
+                                high-water-mark rules itself, carrying the marks per key and topic with the
+                                key's records; every other pattern carries its full NFA state, marks
+                                included, on the general path. */
 
 #define CEP_SESSION_INTERPRET 2  /* runs path: use the built-in kernels, which interpret the pattern's predicates
                                     and folds, instead of kernels compiled for the pattern at cep_session_open
@@ -177,6 +180,34 @@ typedef struct {
                                          session taking a batch those paths accept: bounded work per record, no
                                          runaway keys) fails with CEP_E_UNSUPPORTED before it touches the
                                          session */
+
+#define CEP_BATCH_FILTER 16           /* CEP_SESSION_CARRY sessions on the stencil, chain or runs path: the batch
+                                         may carry null records (valid) and re-delivered offsets.  The library
+                                         applies CEPProcessor.process's two rules on the device, per key in arrival
+                                         order, before it evaluates the admitted records on the session's own path:
+                                         - a record with valid == 0 is dropped (CEPProcessor.java:136-138); it
+                                           neither reads nor moves a mark;
+                                         - in CEP_MODE_PROCESSOR a valid record of topic t is dropped iff offset <
+                                           mark[key][t], else it is admitted and mark[key][t] = offset + 1 (:140,
+                                           :144-145, :152-160).  A mark never set is -1 and admits everything.  In
+                                           CEP_MODE_NFA, or without an offset column, only the null rule applies;
+                                           without a topic column every record is on topic 0;
+                                         CEP_BATCH_OFFSETS_MONOTONE is ignored beside it.  Record positions are those
+                                         of the batch as pushed (base + index, or base + arrival index with
+                                         CEP_BATCH_ARRIVAL_ORDER): dropped records keep theirs and
+                                         cep_stream_position advances by n.  The marks are carried state like the
+                                         halos and tails: topic ids lie in [0, CEP_FILTER_MAX_TOPICS) (a valid record
+                                         outside fails the push with CEP_E_UNSUPPORTED), a push that fails leaves
+                                         them as they were, cep_state_clear clears them, and cep_state_export / evict
+                                         / import / import_keys carry them (blob version 2, written only when a
+                                         covered key has a mark).  A batch without an admitted record is still a
+                                         complete batch: an empty CSR, an advanced position, halos, tails and marks
+                                         untouched.  The push waits once for the device (the admitted count sizes
+                                         the path's launches).  On a general-path carry session the flag does
+                                         nothing -- that path applies both rules already -- so a host may set it
+                                         unconditionally; on a session without CEP_SESSION_CARRY the push fails
+                                         with CEP_E_UNSUPPORTED before it touches the session */
+#define CEP_FILTER_MAX_TOPICS 8
 
 /* One batch of records, struct-of-arrays, grouped by key (each key's records
  * contiguous and in arrival order; or in plain arrival order with CEP_BATCH_ARRIVAL_ORDER).  Replaces a sequence of
@@ -319,6 +350,8 @@ int cep_csr_check(const cep_matches* m, int64_t n_records, int32_t n_names);
  * are collected only before the next push); cep_batch_ready(id) tells without waiting whether batch id's
  * matches are complete (1) or not yet (0).  The host CSR of cep_collect_batch is valid until the next collect. */
 int64_t cep_batch_id(const cep_session* s);
+/* CEP_BATCH_FILTER: records per workgroup of the admission scan (a key's segment may cross any number of them) */
+int32_t cep_filter_tile_records(void);
 int cep_batch_ready(cep_session* s, int64_t id);
 int cep_collect_batch(cep_session* s, int64_t id, cep_matches* out);
 

@@ -342,11 +342,16 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
     if (b->n > 0 && !b->cols[c]) return fail(CEP_E_ARG, "null value column");
   // records the processor would drop (null key/value, re-delivered offsets)
   // break contiguity: the stencil only takes batches without them
-  const bool stencil_batch = !b->valid && !(s->opts.mode == CEP_MODE_PROCESSOR && b->offset &&
-                                            !(b->flags & CEP_BATCH_OFFSETS_MONOTONE));
+  // CEP_BATCH_FILTER: the library drops them itself (filter.hip) and the session's own path takes the rest;
+  // the general path applies both rules already, there the flag does nothing
+  const bool filtered = (b->flags & CEP_BATCH_FILTER) && s->carry && s->path != CEP_PATH_GENERAL;
+  const bool stencil_batch = filtered || (!b->valid && !(s->opts.mode == CEP_MODE_PROCESSOR && b->offset &&
+                                                         !(b->flags & CEP_BATCH_OFFSETS_MONOTONE)));
   // (rejected before any session state changes: cep_batch_id and the last batch's CSR stand)
   if ((b->flags & CEP_BATCH_ARRIVAL_ORDER) && !s->carry)
     return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_ARRIVAL_ORDER needs a CEP_SESSION_CARRY session");
+  if ((b->flags & CEP_BATCH_FILTER) && !s->carry)
+    return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_FILTER needs a CEP_SESSION_CARRY session");
   if ((b->flags & CEP_BATCH_STOP_AT_ERROR) && s->path != CEP_PATH_GENERAL && stencil_batch) {
     static const char* const kPath[] = {"", "stencil", "", "chain", "runs"};
     return fail(CEP_E_UNSUPPORTED, std::string("CEP_BATCH_STOP_AT_ERROR is for general-path batches: this batch runs on "
@@ -370,10 +375,24 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   s->last_gpos = nullptr;
   int rc = CEP_OK;
   const bool arrival = (b->flags & CEP_BATCH_ARRIVAL_ORDER) && b->n > 0;
+  s->arrival_n = arrival ? b->n : 0;
   cep_batch gb;
   const void* gcols[16] = {};
   const int64_t base0 = s->base;
-  if (arrival) {
+  if (filtered && b->n > 0) {                      // [group ->] filter -> the path, over the admitted records
+    cep_batch fb;
+    const void* fcols[16] = {};
+    if (arrival) rc = group_batch(s, b, st, gb, gcols);
+    if (!rc) rc = filter_batch(s, arrival ? &gb : b, st, fb, fcols);
+    if (!rc) rc = push_dispatch(s, &fb, st, true);
+    if (!rc) {
+      // the path took the batch: its marks are committed with it, and the dropped records' positions stay used
+      if (filter_commit_launch(s->f_args, b->n, st) != hipSuccess) rc = fail(CEP_E_HIP, "filter_commit launch failed");
+      s->base = base0 + b->n;
+    }
+    if (!rc && arrival && s->last_path == CEP_PATH_RUNS) rc = arrival_csr(s, base0, b->n, st);
+    s->cur_pos = nullptr;
+  } else if (arrival) {
     rc = group_batch(s, b, st, gb, gcols);
     if (!rc) rc = push_dispatch(s, &gb, st, stencil_batch);
     if (!rc && (s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS)) rc = arrival_csr(s, base0, b->n, st);
@@ -665,6 +684,8 @@ int cep_collect(cep_session* s, cep_matches* o) {
 }
 
 int64_t cep_batch_id(const cep_session* s) { return s ? s->push_id : -1; }
+
+int32_t cep_filter_tile_records(void) { return FILTER_TF; }
 
 // the delivery buffer holding batch `id`, or -1
 static int delivered_slot(const cep_session* s, int64_t id) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 
+#include "../../include/kcep.h"
 #include "kcep_internal.h"
 
 namespace kcep {
@@ -66,6 +67,45 @@ hipError_t arrival_reorder(const int64_t* mrec, const int32_t* mkey, const int64
 hipError_t stencil_arrival_ranks(const int32_t* out, int k, const int64_t* total, int64_t out_cap, const int64_t* gpos,
                                  int64_t base, int64_t n, int64_t* cnt, int32_t* head, int64_t* moff, int64_t* tot,
                                  int64_t* tmp, hipStream_t st);
+// ---- filter.hip: CEP_BATCH_FILTER, the null and high-water-mark rules on a key-grouped device batch ----
+constexpr int FILTER_TF = 1024;                   // records per workgroup of the admission scan (a tile)
+constexpr int FILTER_MAX_TOPICS = CEP_FILTER_MAX_TOPICS;   // marks per key: topic ids in [0, FILTER_MAX_TOPICS)
+struct FilterArgs {
+  // in: the batch (optional columns may be null); pos: its records' stream positions (null: base + index)
+  const int32_t* key;
+  const uint8_t* valid;
+  const int32_t* topic;
+  const int32_t* partition;
+  const int64_t* offset;
+  const int64_t* ts;
+  const int64_t* pos;
+  int64_t base;
+  const void* cols[16];
+  int32_t coltype[16];
+  int32_t ncols;
+  // out: the admitted records, compacted in order (a column the batch lacks is not written)
+  int32_t *o_key, *o_topic, *o_partition;
+  int64_t *o_offset, *o_ts, *o_pos;
+  void* o_cols[16];
+  // the marks: FILTER_MAX_TOPICS per key id (-1: never set); stage: the same shape, this batch's new ones
+  int32_t use_marks;              // 0: only the null rule (CEP_MODE_NFA, or a batch without offsets)
+  int32_t max_keys;
+  int64_t* marks;
+  int64_t* stage;
+  // scratch: per tile a word / FILTER_MAX_TOPICS words / a count / an offset; per record (padded to tiles) a slot
+  int32_t* tile_f;
+  int64_t* tile_v;
+  int32_t* tile_cnt;
+  int64_t* tile_off;
+  uint16_t* slot;
+  int64_t* n_dev;                 // device: the admitted count
+  int64_t* bad;                   // device: a valid record's topic id was out of range
+  int64_t* host;                  // pinned host, by its device address: {admitted count, bad, stamp}
+  int64_t stamp;                  // this batch's number: the host spins until host[2] holds it
+};
+hipError_t filter_launch(const FilterArgs& A, int64_t n, hipStream_t st);
+hipError_t filter_commit_launch(const FilterArgs& A, int64_t n, hipStream_t st);
+
 // The plain stencil kernel without carry stores a super-tile's first ST_DENSE matches (one int each)
 // in a dense region at the head of the slot buffer (super-tile t at t * ST_DENSE) and the rest in
 // the super-tile's own region after it (nsuper * ST_DENSE + t * sub * 4096 + m): the dense runs sit

@@ -2,6 +2,9 @@
 // runs and general batches, their carried pools (carry_gc, tail_reserve), CEP_BATCH_ARRIVAL_ORDER (group.hip).
 #include <string.h>
 
+#include <atomic>
+#include <chrono>
+
 #include "jit.h"
 #include "session.h"
 
@@ -131,7 +134,7 @@ int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st) {
     L.carry = StencilCarry{s->halo.as<HaloHdr>(), s->hpos.as<int64_t>(), SP.k - 1, ++s->halo_stamp,
                            max_keys32(s), s->base,
                            s->hflags.as<unsigned long long>() + (s->halo_stamp & 1), s->cur_pos,
-                           s->cur_pos ? 1 : 0};
+                           s->arrival_n > 0 ? 1 : 0};
     s->last_gpos = s->cur_pos;
     s->halo_base = s->base;
     s->base += b->n;
@@ -160,15 +163,16 @@ int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st) {
     L.deliver.host_cap = s->dl_cap;
     L.deliver.ticket = s->dl_ticket.as<unsigned>();
     L.deliver.stamp = ++s->dl_stamp;
-    if (s->cur_pos && b->n > 0) {                  // arrival order: rows delivered by their completing record's arrival
-      if (s->a_moff.ensure(size_t(b->n) * 8) || s->a_tmp.ensure(size_t(b->n / 1024 + 4) * 8) || s->scal.ensure(64))
+    if (s->arrival_n > 0 && b->n > 0) {            // arrival order: rows delivered by their completing record's arrival
+      const int64_t an = s->arrival_n;               // (the batch as pushed: a filtered one holds fewer records)
+      if (s->a_moff.ensure(size_t(an) * 8) || s->a_tmp.ensure(size_t(an / 1024 + 4) * 8) || s->scal.ensure(64))
         return fail(CEP_E_HIP, "allocation failed");
       L.deliver.a_cnt = s->a_cnt.as<int64_t>();
       L.deliver.a_head = s->a_head.as<int32_t>();
       L.deliver.a_moff = s->a_moff.as<int64_t>();
       L.deliver.a_tot = s->scal.as<int64_t>() + 6;
       L.deliver.a_tmp = s->a_tmp.as<int64_t>();
-      L.deliver.a_n = b->n;
+      L.deliver.a_n = an;
     }
     s->delivered = true;
   }
@@ -932,6 +936,100 @@ int arrival_csr(cep_session* s, int64_t base, int64_t n, hipStream_t st) {
   std::swap(s->o_entoff, s->a_entoff);
   std::swap(s->o_name, s->a_name);
   std::swap(s->o_entrec, s->a_entrec);
+  return CEP_OK;
+}
+
+// the high-water marks of a stencil / chain / runs carry session: FILTER_MAX_TOPICS per key id, none set
+// (allocated at the first filtered push, or by an imported blob that carries marks)
+int marks_ensure(cep_session* s, hipStream_t st) {
+  if (s->f_marks.p) return CEP_OK;
+  const size_t bytes = size_t(s->opts.max_keys) * FILTER_MAX_TOPICS * 8;
+  if (s->f_marks.ensure(bytes) || s->f_stage.ensure(bytes)) {
+    s->f_marks.release();
+    return fail(CEP_E_HIP, "mark table allocation failed");
+  }
+  HIPCHECK(hipMemsetAsync(s->f_marks.p, 0xFF, bytes, st));   // -1: the reference's latestOffsets default
+  return CEP_OK;
+}
+
+// CEP_BATCH_FILTER: the key-grouped batch b (the caller's, host or device, or group_batch's output with
+// s->cur_pos) through filter.hip into the session's filtered columns; fb describes them (device memory,
+// no valid column, offsets monotone by construction, fb.n = the admitted records), s->cur_pos = their stream
+// positions.  Waits for the admitted count -- the paths' launches are sized by it -- the way cep_collect
+// waits for a delivery.  The marks are staged; the caller commits them once the path has taken the batch.
+int filter_batch(cep_session* s, const cep_batch* b, hipStream_t st, cep_batch& fb, const void** fcols) {
+  const Program& P = s->pat->prog;
+  const int64_t n = b->n;
+  NfaArgs in{};
+  int rc = stage_inputs(s, b, st, in, true);
+  if (rc) return rc;
+  const bool marks = s->opts.mode == CEP_MODE_PROCESSOR && in.offset;
+  if (marks && (rc = marks_ensure(s, st))) return rc;
+  const size_t nt = size_t((n + FILTER_TF - 1) / FILTER_TF), n4 = size_t(n) * 4, n8 = size_t(n) * 8;
+  if (s->f_tile_f.ensure(nt * 4) || s->f_tile_v.ensure(nt * FILTER_MAX_TOPICS * 8) || s->f_tile_cnt.ensure(nt * 4) ||
+      s->f_tile_off.ensure(nt * 8) || s->f_slot.ensure(nt * FILTER_TF * 2) || s->f_scal.ensure(16) ||
+      s->f_key.ensure(n4) || s->f_pos.ensure(n8) || (in.topic && s->f_topic.ensure(n4)) ||
+      (in.partition && s->f_part.ensure(n4)) || (in.offset && s->f_off.ensure(n8)) || (in.ts && s->f_ts.ensure(n8)))
+    return fail(CEP_E_HIP, "allocation failed");
+  if (!s->f_host) {
+    HIPCHECK(s->f_host.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(s->f_host.p, 0, 64);
+  }
+  FilterArgs F{};
+  F.key = in.key; F.valid = in.valid; F.topic = in.topic; F.partition = in.partition; F.offset = in.offset; F.ts = in.ts;
+  F.pos = s->cur_pos;
+  F.base = s->base;
+  F.ncols = b->n_cols;
+  for (int c = 0; c < b->n_cols; c++) {
+    if (s->f_cols[c].ensure(size_t(n) * type_size(P.coltypes[c]))) return fail(CEP_E_HIP, "allocation failed");
+    F.cols[c] = in.cols[c];
+    F.coltype[c] = P.coltypes[c];
+    F.o_cols[c] = s->f_cols[c].p;
+    fcols[c] = s->f_cols[c].p;
+  }
+  F.o_key = s->f_key.as<int32_t>(); F.o_topic = s->f_topic.as<int32_t>(); F.o_partition = s->f_part.as<int32_t>();
+  F.o_offset = s->f_off.as<int64_t>(); F.o_ts = s->f_ts.as<int64_t>(); F.o_pos = s->f_pos.as<int64_t>();
+  F.use_marks = marks ? 1 : 0;
+  F.max_keys = max_keys32(s);
+  F.marks = s->f_marks.as<int64_t>();
+  F.stage = s->f_stage.as<int64_t>();
+  F.tile_f = s->f_tile_f.as<int32_t>(); F.tile_v = s->f_tile_v.as<int64_t>(); F.tile_cnt = s->f_tile_cnt.as<int32_t>();
+  F.tile_off = s->f_tile_off.as<int64_t>(); F.slot = s->f_slot.as<uint16_t>();
+  F.n_dev = s->f_scal.as<int64_t>();
+  F.bad = s->f_scal.as<int64_t>() + 1;
+  HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&F.host), s->f_host.p, 0));
+  F.stamp = ++s->f_stamp;
+  HIPCHECK(filter_launch(F, n, st));
+  s->f_args = F;
+  // filter_offsets stamps the host words once the count is there: spin on the stamp (a stream wait sleeps
+  // and wakes microseconds late); a stamp that does not come -- a fault -- is left to the stream wait
+  const volatile int64_t* stamp = s->f_host.p + 2;
+  const auto t0 = std::chrono::steady_clock::now();
+  while (*stamp != F.stamp) {
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
+      HIPCHECK(hipStreamSynchronize(st));
+      if (*stamp != F.stamp) return fail(CEP_E_HIP, "the filter kernels did not complete");
+      break;
+    }
+    __builtin_ia32_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  const int64_t adm = s->f_host.p[0];
+  if (s->f_host.p[1])
+    return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_FILTER: a record's topic id is outside [0, CEP_FILTER_MAX_TOPICS)");
+  if (adm < 0 || adm > n) return fail(CEP_E_HIP, "the filter's admitted count is out of range");
+  fb = *b;
+  fb.n = adm;
+  fb.key_id = F.o_key;
+  fb.valid = nullptr;
+  fb.topic = in.topic ? F.o_topic : nullptr;
+  fb.partition = in.partition ? F.o_partition : nullptr;
+  fb.offset = in.offset ? F.o_offset : nullptr;
+  fb.ts = in.ts ? F.o_ts : nullptr;
+  fb.cols = fcols;
+  fb.mem = CEP_MEM_DEVICE;
+  fb.flags = (b->flags & ~uint32_t(CEP_BATCH_FILTER)) | CEP_BATCH_OFFSETS_MONOTONE;
+  s->cur_pos = F.o_pos;
   return CEP_OK;
 }
 

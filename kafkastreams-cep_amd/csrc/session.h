@@ -200,6 +200,16 @@ struct cep_session {
   DBuf g_cols[16];
   const int64_t* cur_pos = nullptr;        // the batch being pushed: stream position per grouped record (else null)
   const int64_t* last_gpos = nullptr;      // ... of the last stencil / chain batch (carry_args)
+  int64_t arrival_n = 0;                   // ... its records if it came in arrival order (CEP_BATCH_ARRIVAL_ORDER), else 0:
+                                           // arrival indices run over them, also where a filter dropped some
+  // ---- CEP_BATCH_FILTER (filter.hip): the high-water marks of stencil / chain / runs carry sessions, per
+  // (key id, topic id), allocated at the first filtered push; the batch's staged marks; the admitted batch ----
+  DBuf f_marks, f_stage, f_tile_f, f_tile_v, f_tile_cnt, f_tile_off, f_slot, f_scal;
+  DBuf f_key, f_topic, f_part, f_off, f_ts, f_pos;
+  DBuf f_cols[16];
+  Pinned<int64_t> f_host;                  // {admitted count, topic-range flag, stamp}, written by the device
+  int64_t f_stamp = 0;                     // the filtered pushes so far
+  kcep::FilterArgs f_args{};               // the last filtered push's (its staged marks are committed by them)
   bool collected = false;                  // the CSR above is the last batch's: a second collect re-uses it
   cep_matches last{};
   std::vector<uint8_t> evict_buf;          // cep_state_evict's blobs
@@ -254,6 +264,8 @@ int push_runs(cep_session* s, const cep_batch* b, hipStream_t st);
 int push_general(cep_session* s, const cep_batch* b, hipStream_t st);
 int group_batch(cep_session* s, const cep_batch* b, hipStream_t st, cep_batch& gb, const void** gcols);
 int arrival_csr(cep_session* s, int64_t base, int64_t n, hipStream_t st);
+int filter_batch(cep_session* s, const cep_batch* b, hipStream_t st, cep_batch& fb, const void** fcols);
+int marks_ensure(cep_session* s, hipStream_t st);
 int carry_gc(cep_session* s, int64_t min_words, hipStream_t st);
 int tail_reserve(cep_session* s, int64_t more, hipStream_t st);
 

@@ -23,8 +23,83 @@ int drain(cep_session* s) {
   return CEP_OK;
 }
 
-// stencil carry sessions: "KCSH", version 1, int64 next stream position, int32 key count, then per key
-// with a halo: int32 key id, int32 records, uint64 stage masks, int64 stream positions[records]
+// ---- the high-water marks of stencil / chain / runs carry sessions (CEP_BATCH_FILTER, filter.hip) ----
+// "KCSH" and "KCSR" blobs of version 2 end with a marks section behind their key entries: int32 count, then
+// per mark int32 key id, int32 topic id, int64 mark.  Version 2 is written only when a covered key has a
+// mark: a session that never took a filtered batch writes version 1, byte for byte as before.
+constexpr int64_t kNoMark = -1;
+// the marks of key ids [key_lo, key_hi) (empty: the session has no mark table yet)
+int marks_download(cep_session* s, int32_t key_lo, int32_t key_hi, std::vector<int64_t>& m) {
+  m.clear();
+  if (!s->f_marks.p || key_hi <= key_lo) return CEP_OK;
+  m.resize(size_t(key_hi - key_lo) * FILTER_MAX_TOPICS);
+  HIPCHECK(hipMemcpy(m.data(), s->f_marks.as<int64_t>() + int64_t(key_lo) * FILTER_MAX_TOPICS, m.size() * 8,
+                     hipMemcpyDeviceToHost));
+  return CEP_OK;
+}
+// appends key k's marks (row: its FILTER_MAX_TOPICS table entries) as section triples; returns how many
+int32_t marks_triples(const int64_t* row, int32_t k, std::vector<uint8_t>& out) {
+  int32_t cnt = 0;
+  for (int32_t t = 0; t < FILTER_MAX_TOPICS; t++) {
+    if (row[t] == kNoMark) continue;
+    const size_t at = out.size();
+    out.resize(at + 16);
+    memcpy(&out[at], &k, 4); memcpy(&out[at + 4], &t, 4); memcpy(&out[at + 8], &row[t], 8);
+    cnt++;
+  }
+  return cnt;
+}
+// the marks section of keys [key_lo, key_hi): count + triples, or empty when none of them has a mark
+int marks_section(cep_session* s, int32_t key_lo, int32_t key_hi, std::vector<uint8_t>& sec) {
+  std::vector<int64_t> m;
+  int rc = marks_download(s, key_lo, key_hi, m);
+  if (rc) return rc;
+  sec.assign(4, 0);
+  int32_t cnt = 0;
+  for (size_t i = 0; i * FILTER_MAX_TOPICS < m.size(); i++)
+    cnt += marks_triples(&m[i * FILTER_MAX_TOPICS], key_lo + int32_t(i), sec);
+  memcpy(&sec[0], &cnt, 4);
+  if (!cnt) sec.clear();
+  return CEP_OK;
+}
+// the section at p[at, len) checked: its triples' count, or -1
+int64_t marks_parse(const uint8_t* p, size_t at, size_t len) {
+  int32_t cnt;
+  if (at + 4 > len) return -1;
+  memcpy(&cnt, p + at, 4);
+  if (cnt < 0 || at + 4 + 16 * size_t(cnt) > len) return -1;
+  return cnt;
+}
+// a version 2 blob's marks section (behind the key entries, at `at`) into the session's table
+int marks_import(cep_session* s, const uint8_t* p, size_t at, size_t len) {
+  const int64_t cnt = marks_parse(p, at, len);
+  if (cnt < 0) return fail(CEP_E_ARG, "truncated marks section in the state blob");
+  struct Mark { int32_t k, t; int64_t v; };
+  std::vector<Mark> ms(static_cast<size_t>(cnt));
+  for (int64_t i = 0; i < cnt; i++) {
+    Mark& m = ms[size_t(i)];
+    memcpy(&m.k, p + at + 4 + 16 * size_t(i), 4); memcpy(&m.t, p + at + 8 + 16 * size_t(i), 4);
+    memcpy(&m.v, p + at + 12 + 16 * size_t(i), 8);
+    if (m.k < 0 || m.k >= s->opts.max_keys || m.t < 0 || m.t >= FILTER_MAX_TOPICS)
+      return fail(CEP_E_ARG, "bad mark in the state blob");
+  }
+  if (!cnt) return CEP_OK;
+  int rc = marks_ensure(s, s->stream);
+  if (rc || (rc = drain(s))) return rc;
+  if (cnt <= 256) {                                // a few keys (cep_state_import_keys): mark by mark
+    for (const Mark& m : ms)
+      HIPCHECK(hipMemcpy(s->f_marks.as<int64_t>() + int64_t(m.k) * FILTER_MAX_TOPICS + m.t, &m.v, 8, hipMemcpyHostToDevice));
+    return CEP_OK;
+  }
+  std::vector<int64_t> tab;
+  if ((rc = marks_download(s, 0, max_keys32(s), tab))) return rc;
+  for (const Mark& m : ms) tab[size_t(m.k) * FILTER_MAX_TOPICS + size_t(m.t)] = m.v;
+  HIPCHECK(hipMemcpy(s->f_marks.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  return CEP_OK;
+}
+
+// stencil carry sessions: "KCSH", version 1 (2: with a marks section), int64 next stream position, int32 key
+// count, then per key with a halo: int32 key id, int32 records, uint64 stage masks, int64 stream positions[records]
 constexpr uint32_t kHaloMagic = 0x4853434Bu;   // "KCSH"
 int halo_newest(const HaloHdr& h) { return h.stamp[1] > h.stamp[0] ? 1 : 0; }
 
@@ -45,11 +120,14 @@ int halo_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_
     const int sl = halo_newest(tab[i]);
     if (tab[i].stamp[sl] > 0 && tab[i].cnt[sl] > 0) { bytes += 16 + 8 * size_t(tab[i].cnt[sl]); nkeys++; }
   }
+  std::vector<uint8_t> sec;
+  if (int rc = marks_section(s, key_lo, key_hi, sec)) return rc;
+  bytes += sec.size();
   *needed = bytes;
   if (!buf) return CEP_OK;
   if (cap < bytes) return fail(CEP_E_ARG, "export buffer too small");
   uint8_t* p = static_cast<uint8_t*>(buf);
-  const uint32_t ver = 1;
+  const uint32_t ver = sec.empty() ? 1 : 2;
   memcpy(p, &kHaloMagic, 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &s->base, 8); memcpy(p + 16, &nkeys, 4);
   p += 20;
   for (size_t i = 0; i < nk; i++) {
@@ -61,10 +139,11 @@ int halo_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_
     memcpy(p + 16, &pos[(2 * i + size_t(sl)) * size_t(km1)], 8 * size_t(cnt));
     p += 16 + 8 * size_t(cnt);
   }
+  if (!sec.empty()) memcpy(p, sec.data(), sec.size());
   return CEP_OK;
 }
 
-int halo_import(cep_session* s, const uint8_t* p, size_t len) {
+int halo_import(cep_session* s, const uint8_t* p, size_t len, uint32_t ver) {
   int64_t base;
   int32_t nkeys;
   memcpy(&base, p + 8, 8); memcpy(&nkeys, p + 16, 4);
@@ -83,6 +162,8 @@ int halo_import(cep_session* s, const uint8_t* p, size_t len) {
     rows.push_back(r);
     at += 16 + 8 * size_t(r.cnt);
   }
+  if (ver == 2)
+    if (int rc = marks_import(s, p, at, len)) return rc;
   if (int rc = drain(s)) return rc;
   for (auto& r : rows) {                         // slot 0 holds the halo, slot 1 is empty
     HaloHdr h{};
@@ -129,7 +210,10 @@ int tail_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_
   std::vector<uint8_t> out(20);
   int32_t nkeys = 0;
   for (int32_t k = key_lo; k < key_hi; k++) nkeys += tail_entry(s, tab, pool, k, out) > 0;
-  const uint32_t ver = 1;
+  std::vector<uint8_t> sec;
+  if ((rc = marks_section(s, key_lo, key_hi, sec))) return rc;
+  out.insert(out.end(), sec.begin(), sec.end());
+  const uint32_t ver = sec.empty() ? 1 : 2;
   memcpy(&out[0], &kTailMagic, 4); memcpy(&out[4], &ver, 4); memcpy(&out[8], &s->base, 8); memcpy(&out[16], &nkeys, 4);
   *needed = out.size();
   if (!buf) return CEP_OK;
@@ -137,7 +221,7 @@ int tail_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_
   memcpy(buf, out.data(), out.size());
   return CEP_OK;
 }
-int tail_import(cep_session* s, const uint8_t* p, size_t len) {
+int tail_import(cep_session* s, const uint8_t* p, size_t len, uint32_t ver) {
   int64_t base;
   int32_t nkeys;
   memcpy(&base, p + 8, 8); memcpy(&nkeys, p + 16, 4);
@@ -155,6 +239,8 @@ int tail_import(cep_session* s, const uint8_t* p, size_t len) {
     recs += size_t(cnt);
     at += 16 + size_t(cnt) * RW * 8;
   }
+  if (ver == 2)
+    if (int rc = marks_import(s, p, at, len)) return rc;
   if (int rc = drain(s)) return rc;
   int rc = tail_reserve(s, int64_t(recs), s->stream);
   if (rc) return rc;
@@ -227,12 +313,14 @@ int cep_state_import(cep_session* s, const void* buf, size_t len) {
   int32_t nkeys;
   memcpy(&magic, p, 4); memcpy(&ver, p + 4, 4); memcpy(&base, p + 8, 8); memcpy(&nkeys, p + 16, 4);
   if (halo_session(s)) {
-    if (magic != kHaloMagic || ver != 1 || nkeys < 0) return fail(CEP_E_ARG, "bad state blob (stencil sessions take KCSH)");
-    return halo_import(s, p, len);
+    if (magic != kHaloMagic || (ver != 1 && ver != 2) || nkeys < 0)
+      return fail(CEP_E_ARG, "bad state blob (stencil sessions take KCSH)");
+    return halo_import(s, p, len, ver);
   }
   if (tail_session(s)) {
-    if (magic != kTailMagic || ver != 1 || nkeys < 0) return fail(CEP_E_ARG, "bad state blob (runs sessions take KCSR)");
-    return tail_import(s, p, len);
+    if (magic != kTailMagic || (ver != 1 && ver != 2) || nkeys < 0)
+      return fail(CEP_E_ARG, "bad state blob (runs sessions take KCSR)");
+    return tail_import(s, p, len, ver);
   }
   if (magic != kStateMagic || ver != 1 || nkeys < 0) return fail(CEP_E_ARG, "bad state blob");
   const DevProgram& D = s->pat->prog.dev;
@@ -280,6 +368,8 @@ int cep_state_clear(cep_session* s) {
   if ((rc = drain(s))) return rc;
   s->base = 0;
   s->stop_uncommitted = 0;
+  if (s->f_marks.p)                                // no key has a mark
+    HIPCHECK(hipMemset(s->f_marks.p, 0xFF, size_t(s->opts.max_keys) * FILTER_MAX_TOPICS * 8));
   if (halo_session(s)) {
     HIPCHECK(hipMemset(s->halo.p, 0, size_t(s->opts.max_keys) * sizeof(HaloHdr)));
     HIPCHECK(hipMemset(s->hflags.p, 0, 16));       // both error-flag words (by stamp parity)
@@ -329,13 +419,31 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
   std::vector<uint8_t>& out = s->evict_buf;
   out.clear();
   offs[0] = 0;
-  const uint32_t ver = 1;
   const int64_t at_pos = s->base - s->stop_uncommitted;
-  auto header = [&](uint32_t magic, int32_t nk) {
+  auto header = [&](uint32_t magic, int32_t nk, uint32_t ver = 1) {
     const size_t at = out.size();
     out.resize(at + 20);
     memcpy(&out[at], &magic, 4); memcpy(&out[at + 4], &ver, 4); memcpy(&out[at + 8], &at_pos, 8);
     memcpy(&out[at + 16], &nk, 4);
+  };
+  // the evicted keys' marks leave with them (a key with marks but no records still gets a blob: version 2,
+  // no key entry)
+  std::vector<int64_t> marks;
+  if ((rc = marks_download(s, 0, max_keys32(s), marks))) return rc;
+  bool marks_dirty = false;
+  auto has_marks = [&](int32_t k) {
+    if (marks.empty()) return false;
+    for (int t = 0; t < FILTER_MAX_TOPICS; t++)
+      if (marks[size_t(k) * FILTER_MAX_TOPICS + size_t(t)] != kNoMark) return true;
+    return false;
+  };
+  auto marks_out = [&](int32_t k) {                // the blob's marks section; the key's marks are cleared
+    const size_t at = out.size();
+    out.resize(at + 4);
+    const int32_t cnt = marks_triples(&marks[size_t(k) * FILTER_MAX_TOPICS], k, out);
+    memcpy(&out[at], &cnt, 4);
+    for (int t = 0; t < FILTER_MAX_TOPICS; t++) marks[size_t(k) * FILTER_MAX_TOPICS + size_t(t)] = kNoMark;
+    marks_dirty = true;
   };
   if (halo_session(s)) {
     const int km1 = s->pat->prog.stencil.k - 1;
@@ -348,13 +456,15 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
       HaloHdr& h = tab[size_t(keys[i])];
       const int sl = halo_newest(h);
       const int32_t cnt = h.cnt[sl];
-      if (h.stamp[sl] > 0 && cnt > 0) {
-        header(kHaloMagic, 1);
+      const bool hm = has_marks(keys[i]), hh = h.stamp[sl] > 0 && cnt > 0;
+      if (hh || hm) header(kHaloMagic, hh ? 1 : 0, hm ? 2 : 1);
+      if (hh) {
         const size_t at = out.size();
         out.resize(at + 16 + 8 * size_t(cnt));
         memcpy(&out[at], &keys[i], 4); memcpy(&out[at + 4], &cnt, 4); memcpy(&out[at + 8], &h.masks[sl], 8);
         memcpy(&out[at + 16], &pos[(2 * size_t(keys[i]) + size_t(sl)) * size_t(km1)], 8 * size_t(cnt));
       }
+      if (hm) marks_out(keys[i]);
       h = HaloHdr{};                                 // no halo: the next batch starts the key afresh
       offs[i + 1] = int64_t(out.size());
     }
@@ -364,10 +474,10 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
     int rc2 = tail_download(s, tab, pool);
     if (rc2) return rc2;
     for (int64_t i = 0; i < n; i++) {
-      if (tab[2 * size_t(keys[i]) + 1] > 0) {
-        header(kTailMagic, 1);
-        tail_entry(s, tab, pool, keys[i], out);
-      }
+      const bool hm = has_marks(keys[i]), ht = tab[2 * size_t(keys[i]) + 1] > 0;
+      if (ht || hm) header(kTailMagic, ht ? 1 : 0, hm ? 2 : 1);
+      if (ht) tail_entry(s, tab, pool, keys[i], out);
+      if (hm) marks_out(keys[i]);
       tab[2 * size_t(keys[i]) + 1] = 0;              // (the pool records are reclaimed by the next compaction)
       offs[i + 1] = int64_t(out.size());
     }
@@ -392,6 +502,7 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
     }
     HIPCHECK(hipMemcpy(s->ctab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
   }
+  if (marks_dirty) HIPCHECK(hipMemcpy(s->f_marks.p, marks.data(), marks.size() * 8, hipMemcpyHostToDevice));
   *blobs = out.data();
   return CEP_OK;
 }
@@ -543,10 +654,10 @@ int cep_state_import_keys(cep_session* s, const void* const* blobs, const size_t
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!blobs || !lens || !keys))) return fail(CEP_E_ARG, "null argument");
   // one multi-key blob with the keys renumbered, then the ordinary import
-  std::vector<uint8_t> all(20);
-  const uint32_t magic = halo_session(s) ? kHaloMagic : tail_session(s) ? kTailMagic : kStateMagic, ver = 1;
+  std::vector<uint8_t> all(20), msec(4);           // msec: the blobs' marks, re-keyed (version 2 blobs)
+  const uint32_t magic = halo_session(s) ? kHaloMagic : tail_session(s) ? kTailMagic : kStateMagic;
   int64_t base = 0;
-  int32_t nk = 0;
+  int32_t nk = 0, nmarks = 0;
   for (int64_t i = 0; i < n; i++) {
     const uint8_t* p = static_cast<const uint8_t*>(blobs[i]);
     if (!p || lens[i] < 20) return fail(CEP_E_ARG, "bad state blob");
@@ -554,14 +665,38 @@ int cep_state_import_keys(cep_session* s, const void* const* blobs, const size_t
     int64_t b;
     int32_t cnt;
     memcpy(&m, p, 4); memcpy(&v, p + 4, 4); memcpy(&b, p + 8, 8); memcpy(&cnt, p + 16, 4);
-    if (m != magic || v != 1 || cnt > 1) return fail(CEP_E_ARG, "cep_state_import_keys takes single-key blobs of this session's kind");
+    const bool v2 = v == 2 && magic != kStateMagic;
+    if (m != magic || (v != 1 && !v2) || cnt < 0 || cnt > 1)
+      return fail(CEP_E_ARG, "cep_state_import_keys takes single-key blobs of this session's kind");
     if (keys[i] < 0 || keys[i] >= s->opts.max_keys) return fail(CEP_E_ARG, "key id out of [0, max_keys)");
     base = std::max(base, b);
+    size_t end = lens[i];                            // of the key entry: a version 2 blob's marks follow it
+    if (v2) {
+      end = 20;
+      if (cnt == 1) {
+        int32_t w = 0, rw = 1;
+        if (lens[i] < 36) return fail(CEP_E_ARG, "truncated state blob");
+        memcpy(&w, p + 24, 4); memcpy(&rw, p + 28, 4);
+        if (w < 0 || (magic == kTailMagic && rw < 0)) return fail(CEP_E_ARG, "bad key entry in the state blob");
+        end = 36 + 8 * size_t(w) * (magic == kTailMagic ? size_t(rw) : 1);
+      }
+      const int64_t mc = end <= lens[i] ? marks_parse(p, end, lens[i]) : -1;
+      if (mc < 0) return fail(CEP_E_ARG, "truncated marks section in the state blob");
+      const size_t at = msec.size();
+      msec.insert(msec.end(), p + end + 4, p + end + 4 + 16 * size_t(mc));
+      for (int64_t q = 0; q < mc; q++) memcpy(&msec[at + 16 * size_t(q)], &keys[i], 4);
+      nmarks += int32_t(mc);
+    }
     if (cnt == 0) continue;
     const size_t at = all.size();
-    all.insert(all.end(), p + 20, p + lens[i]);
+    all.insert(all.end(), p + 20, p + end);
     memcpy(&all[at], &keys[i], 4);
     nk++;
+  }
+  const uint32_t ver = nmarks ? 2 : 1;
+  if (nmarks) {
+    memcpy(&msec[0], &nmarks, 4);
+    all.insert(all.end(), msec.begin(), msec.end());
   }
   memcpy(&all[0], &magic, 4); memcpy(&all[4], &ver, 4); memcpy(&all[8], &base, 8); memcpy(&all[16], &nk, 4);
   return cep_state_import(s, all.data(), all.size());
@@ -570,9 +705,9 @@ int cep_state_import_keys(cep_session* s, const void* const* blobs, const size_t
 int cep_state_positions(const void* buf, size_t len, int64_t* out, int64_t cap, int64_t* n) {
   if (!buf || !n || len < 20) return fail(CEP_E_ARG, "bad state blob");
   const uint8_t* p = static_cast<const uint8_t*>(buf);
-  uint32_t magic;
+  uint32_t magic, ver;
   int32_t nkeys;
-  memcpy(&magic, p, 4); memcpy(&nkeys, p + 16, 4);
+  memcpy(&magic, p, 4); memcpy(&ver, p + 4, 4); memcpy(&nkeys, p + 16, 4);
   if ((magic != kStateMagic && magic != kHaloMagic && magic != kTailMagic) || nkeys < 0) return fail(CEP_E_ARG, "bad state blob");
   int64_t cnt = 0;
   size_t at = 20;
@@ -621,6 +756,8 @@ int cep_state_positions(const void* buf, size_t len, int64_t* out, int64_t cap, 
     }
     at += 8 + 4 * size_t(w);
   }
+  // (version 2: the marks section behind the key entries names no record; it only has to be whole)
+  if (ver == 2 && magic != kStateMagic && marks_parse(p, at, len) < 0) return fail(CEP_E_ARG, "truncated marks section in the state blob");
   *n = cnt;
   return out && cnt > cap ? fail(CEP_E_ARG, "output too small") : CEP_OK;
 }

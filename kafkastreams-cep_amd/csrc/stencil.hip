@@ -683,7 +683,8 @@ hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1
   const bool plain = L.plain && !L.chain && L.k <= 7;
   const SlotFormat F{L.k, plain, L.chain, L.carry.hdr != nullptr, plain && !L.carry.hdr && ST_PLAIN_STAGE,
                      !plain && !L.carry.hdr && ST_KEYED_DENSE, nsuper, sub};
-  if (nsuper <= SMALL_FINISH && D.hdr && L.carry.hdr && D.a_moff && L.n <= ARR_SMALL) {   // a small arrival-order flush
+  // (D.a_n: the arrival indices' range, the batch as pushed; L.n of a filtered batch is smaller)
+  if (nsuper <= SMALL_FINISH && D.hdr && L.carry.hdr && D.a_moff && D.a_n <= ARR_SMALL) {   // a small arrival-order flush
     hipLaunchKernelGGL(stencil_finish_deliver_arrival, dim3(1), dim3(1024), 0, st, L.slots, L.tile_count, nsuper, L.k,
                        L.out, L.out_cap, sub, L.total, L.clear_flag, F, L.key, L.carry, L.n, D.host_cap, D.hdr, D.hkey,
                        D.hpos, D.dkey, D.dpos, D.ticket, D.stamp);

@@ -29,6 +29,8 @@ BATCH_OFFSETS_MONOTONE = 1
 BATCH_DELIVER = 2          # the push is collected at once: matches handed to pinned host memory by the device
 BATCH_ARRIVAL_ORDER = 4    # records in arrival order: grouped by key on the device, matches back in arrival order
 BATCH_STOP_AT_ERROR = 8    # general path: the batch stops at its earliest exception, as the reference's task does
+BATCH_FILTER = 16          # stencil / chain / runs carry sessions: nulls and re-deliveries dropped on the device
+FILTER_MAX_TOPICS = 8      # ... whose marks cover topic ids in [0, FILTER_MAX_TOPICS)
 SESSION_CARRY = 1
 SESSION_INTERPRET = 2
 SESSION_PROFILE = 4
@@ -79,7 +81,8 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_key_profile", "cep_key_hash", "cep_key_shard", "cep_shard_plan", "cep_partition", "cep_gather",
            "cep_match_count_to", "cep_state_evict", "cep_state_import_keys", "cep_state_positions",
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
-           "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped"]
+           "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped",
+           "cep_filter_tile_records"]
 
 _lib = None
 
@@ -139,6 +142,9 @@ def lib():
     L.cep_batch_errors.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     if hasattr(L, "cep_batch_stopped"):     # (KCEP_LIB A/B runs may load an older build)
         L.cep_batch_stopped.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "cep_filter_tile_records"):   # (KCEP_LIB A/B runs may load an older build)
+        L.cep_filter_tile_records.argtypes = []
+        L.cep_filter_tile_records.restype = C.c_int32
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -165,6 +171,11 @@ def lib():
 def check(rc: int):
     if rc != CEP_OK:
         raise CepError(rc, lib().cep_last_error().decode())
+
+
+def filter_tile_records() -> int:
+    """cep_filter_tile_records: records per workgroup of BATCH_FILTER's admission scan."""
+    return int(lib().cep_filter_tile_records())
 
 
 def state_positions(blob: bytes) -> np.ndarray:

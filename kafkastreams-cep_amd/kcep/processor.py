@@ -16,7 +16,12 @@ registers) plays the role of the reference's three stores.
   before anything else, so it neither touches state nor moves the high-water
   mark.
 * **High-water mark** (``:140, 152-160``): evaluated on the device per key and
-  topic, across batches.
+  topic, across batches, on general-path sessions.  Stencil, chain and runs
+  sessions carry records, not NFA state: by default the rule is applied here,
+  record by record, before the push; with ``device_filter=True`` every buffered
+  record is pushed with ``BATCH_FILTER`` and the device applies it, carrying the
+  marks with the session's state (topic ids must then lie in
+  ``[0, native.FILTER_MAX_TOPICS)``).
 * **Keys and topics** are interned to dense ids (``key_id`` for the carry
   session, topic ids from the pattern's ``Schema`` so that ``withTopic`` filters
   keep their ids).  The session holds ``max_keys`` key ids; a batch that needs
@@ -104,7 +109,7 @@ class GpuCEPProcessor:
     def __init__(self, queryName: str, pattern: Union[Pattern, bytes], schema: Schema, decoder: ColumnDecoder,
                  batch_size: int = 1 << 16, max_keys: int = 1 << 20, device: int = 0,
                  mode: int = N.MODE_PROCESSOR, prune_at: int = 1 << 20, max_key_words: int = 0,
-                 stop_at_error: bool = False):
+                 stop_at_error: bool = False, device_filter: bool = False):
         if decoder.schema is not schema and decoder.schema.columns != schema.columns:
             raise ValueError("decoder and pattern use different schemas")
         self.queryName = queryName.lower().replace("\\s+", "")
@@ -117,6 +122,10 @@ class GpuCEPProcessor:
         # instead of running every other key to its end for matches flush() then drops; what is
         # forwarded and raised is the same either way
         self.stop_at_error = bool(stop_at_error)
+        # stencil / chain / runs sessions: the high-water-mark rule on the device (CEP_BATCH_FILTER) instead
+        # of flush()'s per-record loop; the marks are then part of the session's state blobs and
+        # checkpoints carry no "hwm" entry
+        self.device_filter = bool(device_filter)
         self.device = device
         self.mode = mode
         ir = pattern if isinstance(pattern, (bytes, bytearray)) else pattern.to_ir(schema)
@@ -273,7 +282,9 @@ class GpuCEPProcessor:
         self._arrived += len(recs)
         arrival = list(range(len(recs)))                  # the processor-wide arrival index of recs[i] is base + this
         self._flags = 0
-        if self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS):
+        if self.device_filter and self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS):
+            self._flags = N.BATCH_FILTER                  # every record goes: arrival stays the identity
+        elif self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS):
             # the stencil / chain / runs paths carry each key's records (its last K-1, or those
             # from its oldest open run on), not its NFA: the high-water-mark rule
             # (CEPProcessor.checkHighWaterMark :152-160) is applied here, in arrival order, and the
@@ -365,6 +376,11 @@ class GpuCEPProcessor:
         self._check()
         if self._pending:
             raise ProcessorFailed("restore() with buffered records")
+        if self.device_filter and snap.get("hwm") and self.session.path != N.PATH_GENERAL:
+            # host-side marks of a run without device_filter: they are keyed by record key, the device's
+            # by key id inside the state blob; mixing the two would drop or re-admit records silently
+            raise ProcessorFailed("snapshot holds host high-water marks (taken with device_filter=False): "
+                                  "restore it into a processor with device_filter=False")
         # carried high-water marks are (interned topic id, offset) pairs (NFAStates.latestOffsets,
         # NFAStates.java:37): the topic ids must mean the same topics as when the snapshot was taken
         topics = dict(snap.get("topics", {}))

@@ -30,10 +30,11 @@ static size_t copy_out(const cep_matches* m, char** sink, size_t* cap) {
   return need;
 }
 
-/* Pipelined: batch i + 1 is pushed before batch i is collected (cep_collect_batch).
+/* offset / valid: the batches' optional columns (NULL: none), as CEP_BATCH_FILTER flushes carry them.
+ * Pipelined: batch i + 1 is pushed before batch i is collected (cep_collect_batch).
  * out: [total us, push us, collect us, matches] */
 int flush_loop_pipelined(cep_session* s, int64_t nb, int64_t per, const int32_t* key, const int32_t* val,
-                         uint32_t flags, void* stream, double* out) {
+                         uint32_t flags, void* stream, double* out, const int64_t* offset, const uint8_t* valid) {
   double tp = 0, tc = 0;
   int64_t nm = 0, prev = -1;
   size_t cap = 0;
@@ -51,6 +52,8 @@ int flush_loop_pipelined(cep_session* s, int64_t nb, int64_t per, const int32_t*
       b.mem = CEP_MEM_HOST;
       b.cols = cols;
       b.flags = flags;
+      b.offset = offset ? offset + i * per : NULL;
+      b.valid = valid ? valid + i * per : NULL;
       int rc = cep_push_batch(s, &b, stream);
       if (rc) return rc;
     }
@@ -77,7 +80,7 @@ int flush_loop_pipelined(cep_session* s, int64_t nb, int64_t per, const int32_t*
 
 /* out: [total us, push us, collect us, matches] */
 int flush_loop(cep_session* s, int64_t nb, int64_t per, const int32_t* key, const int32_t* val, uint32_t flags,
-               void* stream, double* out) {
+               void* stream, double* out, const int64_t* offset, const uint8_t* valid) {
   double tp = 0, tc = 0;
   int64_t nm = 0;
   size_t cap = 0;
@@ -93,6 +96,8 @@ int flush_loop(cep_session* s, int64_t nb, int64_t per, const int32_t* key, cons
     b.mem = CEP_MEM_HOST;
     b.cols = cols;
     b.flags = flags;
+    b.offset = offset ? offset + i * per : NULL;
+    b.valid = valid ? valid + i * per : NULL;
     const double t0 = now_us();
     int rc = cep_push_batch(s, &b, stream);
     if (rc) return rc;
