@@ -110,17 +110,12 @@ hipError_t filter_commit_launch(const FilterArgs& A, int64_t n, hipStream_t st);
 // in a dense region at the head of the slot buffer (super-tile t at t * ST_DENSE) and the rest in
 // the super-tile's own region after it (nsuper * ST_DENSE + t * sub * 4096 + m): the dense runs sit
 // a few KB apart instead of 196 KB, C2 kernel -7.5 us (profiles/r04_ab_stencil_stores.txt).
-#ifndef KCEP_ST_DENSE
-#define KCEP_ST_DENSE 512                  // (<= 512: the session allocates 512 per tile; A/B builds only)
-#endif
-constexpr int ST_DENSE = KCEP_ST_DENSE;
-// The keyed kernel without carry (C5's chain) the same way, with its aux bytes: a super-tile's first
-// ST_DENSE_KEYED matches at t * ST_DENSE_KEYED ints and, after nsuper of those, their aux bytes at
-// t * ST_DENSE_KEYED; the rest in the super-tile's own region (ints, then aux bytes) after both.
-constexpr int ST_DENSE_KEYED = 1024;
-#ifndef ST_KEYED_DENSE
-#define ST_KEYED_DENSE 0                   // A/B knob (builds only; off: kernel -16 us, step +5 us on C5)
-#endif
+constexpr int ST_DENSE = 512;
+// What the session allocates per tile for that region, in ints, on top of the tiles' own slots.  Only
+// ST_DENSE of it is addressed by the layout above (a super-tile is at least one tile); the rest is
+// what a removed keyed dense layout needed, kept so that the allocation stays what it was.
+constexpr int ST_SLOT_DENSE_ALLOC = 1280;
+static_assert(ST_DENSE <= ST_SLOT_DENSE_ALLOC, "the dense region lies inside its allocation");
 
 struct StencilLaunch {
   const int32_t* key;
@@ -129,7 +124,7 @@ struct StencilLaunch {
   int64_t n;
   const StencilProgram* prog_dev;
   int k, coltype, use_topic, chain;
-  int32_t* slots;                 // per-tile match slots, ST_TILE * k ints each (+ ST_DENSE per tile, see below)
+  int32_t* slots;                 // per-tile match slots, ST_TILE * k ints each (+ ST_SLOT_DENSE_ALLOC per tile, see above)
   int64_t* tile_count;            // matches per tile
   int64_t* tile_pre;              // their exclusive prefix
   int64_t* scan_tmp;

@@ -4,73 +4,91 @@
 
 namespace kcep {
 
-hipError_t stencil_count_k1(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k2(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k3(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k4(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k5(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k6(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k7(const StencilLaunch& L, hipStream_t st);
-hipError_t stencil_count_k8(const StencilLaunch& L, hipStream_t st);
+// k in 1..MAXK as a compile-time constant: f(std::integral_constant<int, k>), else hipErrorInvalidValue
+template <int MAXK, class Fn>
+static inline hipError_t with_k(int k, Fn&& f) {
+  if constexpr (MAXK == 0) return hipErrorInvalidValue;
+  else return k == MAXK ? f(std::integral_constant<int, MAXK>{}) : with_k<MAXK - 1>(k, f);
+}
+
+// Exclusive prefix of x over the workgroup's threads (whole waves, at most 16), shuffle-up within the
+// wave and the wave sums through s_w (one barrier; the caller keeps s_w free until it)
+template <class T, class W>
+__device__ __forceinline__ T block_scan_excl(T x, W* s_w, int lane, int wid) {
+  T incl = x;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T y = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += y;
+  }
+  if (lane == 63) s_w[wid] = incl;
+  __syncthreads();
+  T run = incl - x;
+  for (int w = 0; w < wid; w++) run += T(s_w[w]);
+  return run;
+}
 
 // Tiles' match slots -> one contiguous output in record order (the order
 // context.forward sees them, CEPProcessor.java:148): tile t's matches start at
-// the exclusive prefix of the tile counts.  One workgroup per tile.
-// The slot of super-tile t holds one int per match -- the plain kernel: its first record (the
-// stages are consecutive records); the keyed kernel: its completing record, with an aux byte per
-// match after the super-tile's sub x 4096 ints (stencil_row) -- written out as k-int rows.
+// the exclusive prefix of the tile counts.
+// The slot of super-tile t holds one int per match, written out as k-int rows.  Four formats, by the
+// kernel that ran (stencil_kernel.h):
+//   plain_dense  the plain kernel without carry: the match's first record (the stages are consecutive
+//                records); the first ST_DENSE matches in the dense region, the rest in the super-tile's
+//                own region after all dense regions (launch.h ST_DENSE)
+//   plain_carry  the plain kernel with carry, in the super-tile's own slot: the first record, or for a
+//                boundary match -(1 + completing record) with its halo record count in the aux byte
+//   keyed        the keyed kernel, strict pattern, with or without carry: the completing record, aux
+//                byte (k > 1): the stages taken from the halo
+//   chain        the keyed kernel, chain pattern, with or without carry: the completing record, aux
+//                byte: start distance | consumed stages << 2 | halo records << 6 (stencil_row)
+// The aux bytes follow the super-tile's sub x 4096 ints.
+enum class Slot : int { plain_dense, plain_carry, keyed, chain };
 struct SlotFormat {
-  int k, plain, chain, carry, dense, kdense;
+  Slot kind;
+  int k, carry;
   int64_t nsuper;
   int sub;
-  // match m of super-tile t (c matches): its slot word and aux byte, then stage s of its row from them
-  __device__ __forceinline__ void load(const int32_t* slots, int64_t t, int64_t c, int64_t m, int32_t& v,
-                                       uint32_t& a) const {
+  // match m of super-tile t: its slot word and aux byte, then stage s of its row from them
+  __device__ __forceinline__ void load(const int32_t* slots, int64_t t, int64_t m, int32_t& v, uint32_t& a) const {
     a = 0;
-    if (dense) {
+    if (kind == Slot::plain_dense) {
       v = m < ST_DENSE ? slots[t * ST_DENSE + m] : slots[nsuper * ST_DENSE + t * int64_t(sub) * ST_TILE + m];
       return;
     }
-    if (kdense && c <= ST_DENSE_KEYED) {
-      const int64_t i = t * ST_DENSE_KEYED + m;
-      v = slots[i];
-      a = reinterpret_cast<const uint8_t*>(slots + nsuper * ST_DENSE_KEYED)[i];
-      return;
-    }
-    const int32_t* src = slots + (kdense ? nsuper * (ST_DENSE_KEYED + ST_DENSE_KEYED / 4) : 0) +
-                         t * int64_t(sub) * ST_TILE * k;
+    const int32_t* src = slots + t * int64_t(sub) * ST_TILE * k;
     const uint8_t* aux = reinterpret_cast<const uint8_t*>(src + int64_t(sub) * ST_TILE);
     v = src[m];
-    if (plain ? (carry && v < 0) : k > 1) a = aux[m];
+    if (kind == Slot::plain_carry ? v < 0 : k > 1) a = aux[m];
   }
   __device__ __forceinline__ int32_t value(int32_t v, uint32_t a, int s) const {
-    if (dense) return v + s;
-    if (plain) {                                 // first record; carry boundary: -(1 + completing record)
-      if (!carry || v >= 0) return v + s;
+    if (kind == Slot::plain_dense || (kind == Slot::plain_carry && v >= 0)) return v + s;
+    if (kind == Slot::plain_carry) {             // a boundary match
       const int need = int(a);
       return s < need ? -(1 + (need - s)) : -(1 + v) - (k - 1) + s;
     }
-    return stencil_row(v, a, s, k, chain, carry);
+    return stencil_row(v, a, s, k, kind == Slot::chain, carry);
   }
-  // match m of super-tile t (c matches), stage s
-  __device__ __forceinline__ int32_t entry(const int32_t* slots, int64_t t, int64_t c, int64_t m, int s) const {
-    if (dense)                                   // the plain kernel without carry (launch.h ST_DENSE)
-      return (m < ST_DENSE ? slots[t * ST_DENSE + m] : slots[nsuper * ST_DENSE + t * int64_t(sub) * ST_TILE + m]) + s;
-    if (kdense && c <= ST_DENSE_KEYED) {         // the keyed kernel without carry (launch.h)
-      const int64_t i = t * ST_DENSE_KEYED + m;
-      return stencil_row(slots[i], reinterpret_cast<const uint8_t*>(slots + nsuper * ST_DENSE_KEYED)[i], s, k, chain,
-                         carry);
-    }
-    const int32_t* src = slots + (kdense ? nsuper * (ST_DENSE_KEYED + ST_DENSE_KEYED / 4) : 0) +
-                         t * int64_t(sub) * ST_TILE * k;
-    const uint8_t* aux = reinterpret_cast<const uint8_t*>(src + int64_t(sub) * ST_TILE);
-    const int32_t v = src[m];
-    if (plain) {                                 // first record; carry boundary: -(1 + completing record)
-      if (!carry || v >= 0) return v + s;
-      const int need = aux[m];
-      return s < need ? -(1 + (need - s)) : -(1 + v) - (k - 1) + s;
-    }
-    return stencil_row(v, k > 1 ? aux[m] : 0u, s, k, chain, carry);
+};
+
+// A match's row entries as stream positions (carry sessions).  Once per match, from its key id: the
+// range check (a key id outside [0, max_keys) set error flag bit 0 and the host fails the batch: no
+// halo lookup), the halo slot the batch read (kcep_internal.h halo_old) and that slot's positions.
+// Then per row entry r: a batch record (r >= 0) -> its stream position; -1 (a skipped optional stage)
+// or a key out of range -> -1; -(1 + d) -> the halo record d records before the key's segment.
+struct HaloRow {
+  const HaloHdr* h;
+  const int64_t* hp;
+  int old;
+  bool kok;
+  __device__ __forceinline__ HaloRow(const StencilCarry& C, int32_t kk) {
+    kok = kk >= 0 && kk < C.max_keys;
+    h = kok ? C.hdr + kk : nullptr;
+    old = kok ? halo_old(*h, C.stamp) : 0;
+    hp = kok ? C.pos + (2 * int64_t(kk) + old) * C.km1 : nullptr;
+  }
+  __device__ __forceinline__ int64_t pos(const StencilCarry& C, int32_t r) const {
+    return r >= 0 ? halo_gpos(C, r) : (r == -1 || !kok ? -1 : hp[h->cnt[old] - (-r - 1)]);
   }
 };
 // One thread per match: its slot word (and aux byte) loaded once, its k row entries stored (a wave's
@@ -118,9 +136,8 @@ __global__ __launch_bounds__(256) void stencil_gather_dense(const int32_t* __res
 
 // Every other slot format (keyed / chain / carry), K a template parameter, the same batching: a
 // thread's first GATHER_B matches' slot words and aux bytes loaded before any row is stored.  The
-// format's branches are taken once per workgroup (uniform) around loads of one shape each: a value
-// loaded in either arm of a branch is merged after it, and that merge waits for every outstanding
-// memory operation
+// loads have one shape, with no branch on the format around them: a value loaded in either arm of a
+// branch is merged after it, and that merge waits for every outstanding memory operation
 template <int K, class Ld>
 __device__ __forceinline__ void gather_rows(int32_t* __restrict__ dst, int64_t c, const SlotFormat& F, Ld&& ld) {
   const int64_t cb = c < int64_t(GATHER_B) * blockDim.x ? c : int64_t(GATHER_B) * blockDim.x;
@@ -155,38 +172,14 @@ __global__ __launch_bounds__(256) void stencil_gather_k(const int32_t* __restric
   const int64_t c = cnt[t], p = pre[t];
   if (p + c > out_cap || c <= 0) return;
   int32_t* const dst = out + p * K;
-  if (F.kdense && c <= ST_DENSE_KEYED) {         // the keyed kernel's dense region (no carry)
-    const int32_t* const w0 = slots + t * ST_DENSE_KEYED;
-    const uint8_t* const a0 = reinterpret_cast<const uint8_t*>(slots + F.nsuper * ST_DENSE_KEYED) + t * ST_DENSE_KEYED;
-    gather_rows<K>(dst, c, F, [&](int64_t m, int32_t& v, uint32_t& a) { v = w0[m]; a = a0[m]; });
-    return;
-  }
-  const int32_t* const src = slots + (F.kdense ? F.nsuper * (ST_DENSE_KEYED + ST_DENSE_KEYED / 4) : 0) +
-                             t * int64_t(F.sub) * ST_TILE * K;
+  const int32_t* const src = slots + t * int64_t(F.sub) * ST_TILE * K;
   const uint8_t* const aux = reinterpret_cast<const uint8_t*>(src + int64_t(F.sub) * ST_TILE);
   // the aux byte: keyed rows always (k > 1); plain rows only for a carry boundary match (v < 0) -- loaded
   // whenever the format has it (K > 1: inside the slot) and used only then
-  const bool has_aux = K > 1 && (!F.plain || F.carry);
-  if (has_aux)
+  if constexpr (K > 1)
     gather_rows<K>(dst, c, F, [&](int64_t m, int32_t& v, uint32_t& a) { v = src[m]; a = aux[m]; });
   else
     gather_rows<K>(dst, c, F, [&](int64_t m, int32_t& v, uint32_t& a) { v = src[m]; a = 0; });
-}
-
-__global__ __launch_bounds__(256) void stencil_gather(const int32_t* __restrict__ slots, const int64_t* __restrict__ cnt,
-                                                      const int64_t* __restrict__ pre, int32_t* __restrict__ out,
-                                                      int64_t out_cap, int sub, SlotFormat F) {
-  const int64_t t = blockIdx.x;                  // super-tile
-  const int k = F.k;
-  const int64_t c = cnt[t], p = pre[t];
-  if (p + c > out_cap) return;
-  int32_t* const dst = out + p * k;
-  for (int64_t m = threadIdx.x; m < c; m += blockDim.x) {
-    int32_t v;
-    uint32_t a;
-    F.load(slots, t, c, m, v, a);
-    for (int s = 0; s < k; s++) dst[m * k + s] = F.value(v, a, s);
-  }
 }
 
 // ---- launcher ------------------------------------------------------------
@@ -216,16 +209,7 @@ __global__ __launch_bounds__(1024) void tile_scan(const int64_t* __restrict__ cn
       for (int i = 0; i < 8; i++) sum += v[i];
     }
   }
-  int64_t incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  int64_t run = incl - sum;
-  for (int w = 0; w < wid; w++) run += s_w[w];
+  int64_t run = block_scan_excl(sum, s_w, lane, wid);
   if (one_pass) {
 #pragma unroll
     for (int i = 0; i < 8; i++)
@@ -259,16 +243,7 @@ __global__ __launch_bounds__(1024) void stencil_finish_small(const int32_t* __re
   __shared__ int64_t s_w[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int64_t c = tid < nt ? cnt[tid] : 0;
-  int64_t incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  int64_t run = incl - c;
-  for (int w = 0; w < wid; w++) run += s_w[w];
+  const int64_t run = block_scan_excl(c, s_w, lane, wid);
   s_pre[tid] = run;
   if (tid == 1023) { s_pre[SMALL_FINISH] = run + c; *total = run + c; }
   if (tid == 0 && clear_flag) *clear_flag = 0;    // carry: the next batch's error-flag word (the kernel is done)
@@ -280,7 +255,7 @@ __global__ __launch_bounds__(1024) void stencil_finish_small(const int32_t* __re
     for (int64_t q = lane; q < m; q += 64) {               // a match's slot word (and aux byte) loaded once
       int32_t v;
       uint32_t a;
-      F.load(slots, t, m, q, v, a);
+      F.load(slots, t, q, v, a);
       for (int s2 = 0; s2 < k; s2++) dst[q * k + s2] = F.value(v, a, s2);
     }
   }
@@ -466,7 +441,7 @@ __global__ __launch_bounds__(256) void stencil_finish_deliver(const int32_t* __r
       const int64_t i = pre + q;
       int32_t row[STENCIL_MAX_K], last = 0, v;
       uint32_t av;
-      F.load(slots, t, m, q, v, av);                 // (once per match, not once per stage)
+      F.load(slots, t, q, v, av);                    // (once per match, not once per stage)
 #pragma unroll
       for (int s = 0; s < STENCIL_MAX_K; s++)
         if (s < k) {
@@ -475,19 +450,12 @@ __global__ __launch_bounds__(256) void stencil_finish_deliver(const int32_t* __r
           last = row[s];
         }
       const int32_t kk = key[last];
-      // a key id outside [0, max_keys) (error flag bit 0, the host fails the batch): no halo lookup
-      const bool kok = kk >= 0 && kk < C.max_keys;
-      const HaloHdr* h = kok ? C.hdr + kk : nullptr;
-      const int old = kok ? halo_old(*h, C.stamp) : 0;
-      const int64_t* hp = kok ? C.pos + (2 * int64_t(kk) + old) * C.km1 : nullptr;
+      const HaloRow H(C, kk);
       const bool host = i < host_cap;
       int64_t* p = host ? hpos + i * k : dpos + i * k;
 #pragma unroll
       for (int s = 0; s < STENCIL_MAX_K; s++)
-        if (s < k) {
-          const int32_t r = row[s];
-          p[s] = r >= 0 ? halo_gpos(C, r) : (r == -1 || !kok ? -1 : hp[h->cnt[old] - (-r - 1)]);
-        }
+        if (s < k) p[s] = H.pos(C, row[s]);
       if (host) hkey[i] = kk;
       else dkey[i] = kk;
     }
@@ -506,7 +474,7 @@ constexpr int ARR_SMALL = 65536;
 __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
     const int32_t* __restrict__ slots, const int64_t* __restrict__ cnt, int64_t nt, int k, int32_t* __restrict__ out,
     int64_t out_cap, int sub, int64_t* __restrict__ total, unsigned long long* __restrict__ clear_flag, SlotFormat F,
-    const int32_t* __restrict__ key, StencilCarry C, int64_t n, int64_t host_cap, int64_t* __restrict__ hdr,
+    const int32_t* __restrict__ key, StencilCarry C, int64_t host_cap, int64_t* __restrict__ hdr,
     int32_t* __restrict__ hkey, int64_t* __restrict__ hpos, int32_t* __restrict__ dkey, int64_t* __restrict__ dpos,
     unsigned* ticket, int64_t stamp) {
   __shared__ int64_t s_pre[SMALL_FINISH + 1];
@@ -515,17 +483,8 @@ __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
   __shared__ uint32_t s_tpre[1024];              // matches completing at records before thread t's 64
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int64_t c0 = tid < nt ? cnt[tid] : 0;
-  int64_t incl = c0;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
   for (int i = tid; i < ARR_SMALL / 4; i += 1024) s_cnt[i] = 0;
-  __syncthreads();
-  int64_t run = incl - c0;
-  for (int w = 0; w < wid; w++) run += s_w[w];
+  const int64_t run = block_scan_excl(c0, s_w, lane, wid);   // (its barrier: s_cnt zeroed as well)
   s_pre[tid] = run;
   if (tid == 1023) s_pre[SMALL_FINISH] = run + c0;
   __syncthreads();
@@ -551,7 +510,7 @@ __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
       for (int64_t q = lane; q < m; q += 64, it++) {
         int32_t v;
         uint32_t a;
-        F.load(slots, t, m, q, v, a);
+        F.load(slots, t, q, v, a);
         const int32_t last = F.value(v, a, k - 1);
         const int64_t arr = C.gpos[last] - C.base;
         const int32_t kk = key[last];
@@ -570,18 +529,8 @@ __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
       const uint32_t w = s_cnt[tid * 16 + j];
       sum += (w & 0xFF) + ((w >> 8) & 0xFF) + ((w >> 16) & 0xFF) + (w >> 24);
     }
-    uint32_t x = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
     __syncthreads();                               // (s_w reused)
-    if (lane == 63) s_w[wid] = x;
-    __syncthreads();
-    uint32_t before = x - sum;
-    for (int w = 0; w < wid; w++) before += uint32_t(s_w[w]);
-    s_tpre[tid] = before;
+    s_tpre[tid] = block_scan_excl(sum, s_w, lane, wid);
   }
   __syncthreads();
   // pass B: the rows (kept on the device for cep_checksum) and their delivery at the arrival rank
@@ -596,7 +545,7 @@ __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
 #pragma unroll
       for (int u = 0; u < FA_KEEP; u++)
         if (u == it) { v = kv[u]; av = ka[u]; a = karr[u]; kk = kk_[u]; }
-      if (it >= FA_KEEP) F.load(slots, t, m, q, v, av);
+      if (it >= FA_KEEP) F.load(slots, t, q, v, av);
       int32_t row[STENCIL_MAX_K], last = 0;
 #pragma unroll
       for (int s2 = 0; s2 < STENCIL_MAX_K; s2++)
@@ -615,25 +564,23 @@ __global__ __launch_bounds__(1024) void stencil_finish_deliver_arrival(
         j += (w & 0xFF) + ((w >> 8) & 0xFF) + ((w >> 16) & 0xFF) + (w >> 24);
       }
       for (int64_t b = a & ~int64_t(3); b < a; b++) j += (s_cnt[b >> 2] >> (8 * (b & 3))) & 0xFF;
-      if (F.chain)                                 // (a strict fixed-length pattern: one match per record)
-        for (int64_t p = q - 1; p >= 0 && F.entry(slots, t, m, p, k - 1) == last; p--) j++;   // same record, earlier
-      const bool kok = kk >= 0 && kk < C.max_keys;
-      const HaloHdr* h = kok ? C.hdr + kk : nullptr;
-      const int old = kok ? halo_old(*h, C.stamp) : 0;
-      const int64_t* hp = kok ? C.pos + (2 * int64_t(kk) + old) * C.km1 : nullptr;
+      if (F.kind == Slot::chain)                   // (a strict fixed-length pattern: one match per record)
+        for (int64_t p = q - 1; p >= 0; p--, j++) {   // same record, earlier
+          int32_t pv;
+          uint32_t pa;
+          F.load(slots, t, p, pv, pa);
+          if (F.value(pv, pa, k - 1) != last) break;
+        }
+      const HaloRow H(C, kk);
       const bool host = j < host_cap;
       int64_t* pp = host ? hpos + j * k : dpos + j * k;
 #pragma unroll
       for (int s2 = 0; s2 < STENCIL_MAX_K; s2++)
-        if (s2 < k) {
-          const int32_t r = row[s2];
-          pp[s2] = r >= 0 ? halo_gpos(C, r) : (r == -1 || !kok ? -1 : hp[h->cnt[old] - (-r - 1)]);
-        }
+        if (s2 < k) pp[s2] = H.pos(C, row[s2]);
       if (host) hkey[j] = kk;
       else dkey[j] = kk;
     }
   }
-  (void)n;
   deliver_done(ticket, 1u, hdr, stamp);
 }
 
@@ -680,13 +627,14 @@ hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1
   if (e == hipSuccess && ev1) e = hipEventRecord(ev1, st);
   if (e != hipSuccess) return e;
   // the kernel that ran (stencil_kernel.h launch_kts) and its slot format
-  const bool plain = L.plain && !L.chain && L.k <= 7;
-  const SlotFormat F{L.k, plain, L.chain, L.carry.hdr != nullptr, plain && !L.carry.hdr && ST_PLAIN_STAGE,
-                     !plain && !L.carry.hdr && ST_KEYED_DENSE, nsuper, sub};
+  const bool plain = L.plain && !L.chain && L.k <= 7, carry = L.carry.hdr != nullptr;
+  const SlotFormat F{plain ? (carry ? Slot::plain_carry : Slot::plain_dense) : L.chain ? Slot::chain : Slot::keyed,
+                     L.k, carry, nsuper, sub};
+  const bool dense = F.kind == Slot::plain_dense;
   // (D.a_n: the arrival indices' range, the batch as pushed; L.n of a filtered batch is smaller)
   if (nsuper <= SMALL_FINISH && D.hdr && L.carry.hdr && D.a_moff && D.a_n <= ARR_SMALL) {   // a small arrival-order flush
     hipLaunchKernelGGL(stencil_finish_deliver_arrival, dim3(1), dim3(1024), 0, st, L.slots, L.tile_count, nsuper, L.k,
-                       L.out, L.out_cap, sub, L.total, L.clear_flag, F, L.key, L.carry, L.n, D.host_cap, D.hdr, D.hkey,
+                       L.out, L.out_cap, sub, L.total, L.clear_flag, F, L.key, L.carry, D.host_cap, D.hdr, D.hkey,
                        D.hpos, D.dkey, D.dpos, D.ticket, D.stamp);
     return hipGetLastError();
   }
@@ -699,22 +647,15 @@ hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1
   if (nsuper <= SMALL_FINISH) {
     hipLaunchKernelGGL(stencil_finish_small, dim3(1), dim3(1024), 0, st, L.slots, L.tile_count, nsuper, L.k, L.out,
                        L.out_cap, sub, L.total, L.clear_flag, F);
-  } else if (F.dense && nsuper <= FIN_MAX_SUPER && !L.split_finish) {
+  } else if (dense && nsuper <= FIN_MAX_SUPER && !L.split_finish) {
     // the plain kernel without carry (no clear_flag), the range tile_scan served: scan and gather in one
     // launch over the 16-bit counts (KCEP_STENCIL_SPLIT_FINISH=1: the two launches below)
-    decltype(&stencil_finish_dense<1>) f = nullptr;
-    switch (L.k) {
-      case 1: f = stencil_finish_dense<1>; break;
-      case 2: f = stencil_finish_dense<2>; break;
-      case 3: f = stencil_finish_dense<3>; break;
-      case 4: f = stencil_finish_dense<4>; break;
-      case 5: f = stencil_finish_dense<5>; break;
-      case 6: f = stencil_finish_dense<6>; break;
-      case 7: f = stencil_finish_dense<7>; break;
-      default: return hipErrorInvalidValue;       // (the plain kernel: k <= 7)
-    }
-    hipLaunchKernelGGL(f, dim3(unsigned((nsuper + FIN_G - 1) / FIN_G)), dim3(FIN_THREADS), 0, st, L.slots,
-                       L.tile_count16, L.out, L.out_cap, int(nsuper), sub, L.total);
+    e = with_k<7>(L.k, [&](auto K) {   // (the plain kernel: k <= 7)
+      hipLaunchKernelGGL(stencil_finish_dense<decltype(K)::value>, dim3(unsigned((nsuper + FIN_G - 1) / FIN_G)), dim3(FIN_THREADS), 0,
+                         st, L.slots, L.tile_count16, L.out, L.out_cap, int(nsuper), sub, L.total);
+      return hipSuccess;
+    });
+    if (e != hipSuccess) return e;
   } else {
     if (nsuper <= 8 * 1024) {
       hipLaunchKernelGGL(tile_scan, dim3(1), dim3(1024), 0, st, L.tile_count, nsuper, L.tile_pre, L.total, L.clear_flag);
@@ -725,41 +666,16 @@ hipError_t stencil_launch(const StencilLaunch& L, hipEvent_t ev0, hipEvent_t ev1
       if (e == hipSuccess && L.clear_flag) e = hipMemsetAsync(L.clear_flag, 0, 8, st);
       if (e != hipSuccess) return e;
     }
-    if (F.dense) {
-      decltype(&stencil_gather_dense<1>) g = nullptr;
-      switch (L.k) {
-        case 1: g = stencil_gather_dense<1>; break;
-        case 2: g = stencil_gather_dense<2>; break;
-        case 3: g = stencil_gather_dense<3>; break;
-        case 4: g = stencil_gather_dense<4>; break;
-        case 5: g = stencil_gather_dense<5>; break;
-        case 6: g = stencil_gather_dense<6>; break;
-        case 7: g = stencil_gather_dense<7>; break;
-        default: return hipErrorInvalidValue;     // (the plain kernel: k <= 7)
-      }
-      hipLaunchKernelGGL(g, dim3(unsigned(nsuper)), dim3(128), 0, st, L.slots, L.tile_count, L.tile_pre, L.out,
-                         L.out_cap, nsuper, sub);
-    } else {
-      decltype(&stencil_gather_k<1>) g = nullptr;
-      switch (L.k) {
-        case 1: g = stencil_gather_k<1>; break;
-        case 2: g = stencil_gather_k<2>; break;
-        case 3: g = stencil_gather_k<3>; break;
-        case 4: g = stencil_gather_k<4>; break;
-        case 5: g = stencil_gather_k<5>; break;
-        case 6: g = stencil_gather_k<6>; break;
-        case 7: g = stencil_gather_k<7>; break;
-        case 8: g = stencil_gather_k<8>; break;
-        default: break;
-      }
-      if (g) {
-        hipLaunchKernelGGL(g, dim3(unsigned(nsuper)), dim3(128), 0, st, L.slots, L.tile_count, L.tile_pre, L.out,
-                           L.out_cap, F);
-      } else {
-        hipLaunchKernelGGL(stencil_gather, dim3(unsigned(nsuper)), dim3(128), 0, st, L.slots, L.tile_count, L.tile_pre,
-                           L.out, L.out_cap, sub, F);
-      }
-    }
+    e = dense ? with_k<7>(L.k, [&](auto K) {   // (the plain kernel: k <= 7)
+      hipLaunchKernelGGL(stencil_gather_dense<decltype(K)::value>, dim3(unsigned(nsuper)), dim3(128), 0, st, L.slots,
+                         L.tile_count, L.tile_pre, L.out, L.out_cap, nsuper, sub);
+      return hipSuccess;
+    }) : with_k<STENCIL_MAX_K>(L.k, [&](auto K) {
+      hipLaunchKernelGGL(stencil_gather_k<decltype(K)::value>, dim3(unsigned(nsuper)), dim3(128), 0, st, L.slots,
+                         L.tile_count, L.tile_pre, L.out, L.out_cap, F);
+      return hipSuccess;
+    });
+    if (e != hipSuccess) return e;
   }
   if (D.hdr) {
     hipError_t e = hipGetLastError();
@@ -807,18 +723,12 @@ __global__ void stencil_resolve(const int32_t* __restrict__ key, const int32_t* 
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= nm) return;
   const int32_t last = out[i * k + k - 1];
-  const int32_t kk = key[last];
-  const HaloHdr& h = C.hdr[kk];
-  const int old = halo_old(h, C.stamp);
-  const int64_t* hp = C.pos + (2 * int64_t(kk) + old) * C.km1;
-  for (int s = 0; s < k; s++) {
-    const int32_t r = out[i * k + s];
-    pos[i * k + s] = r >= 0 ? halo_gpos(C, r) : (r == -1 ? -1 : hp[h.cnt[old] - (-r - 1)]);
-  }
+  const HaloRow H(C, key[last]);
+  for (int s = 0; s < k; s++) pos[i * k + s] = H.pos(C, out[i * k + s]);
 }
 // CEP_BATCH_DELIVER (a carry session's flush, GpuCEPProcessor): the batch's matches handed to pinned host
 // memory by the device itself, right after the scan -- the header {match count, this batch's error
-// flags}, then per match its key id and its k entries as stream positions (stencil_resolve's rule) --
+// flags}, then per match its key id and its k entries as stream positions (HaloRow) --
 // so that cep_collect is one wait instead of one host round trip per post-processing step.  Matches
 // past host_cap go to the device arrays (dkey / dpos), which cep_collect copies.  The match count is
 // read on the device: the grid strides over the session's capacity.
@@ -839,10 +749,7 @@ __global__ __launch_bounds__(256) void stencil_deliver(const int32_t* __restrict
   for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < nm; i += int64_t(gridDim.x) * blockDim.x) {
     const int32_t last = out[i * k + k - 1];
     const int32_t kk = key[last];
-    const bool kok = kk >= 0 && kk < C.max_keys;   // else error flag bit 0: the host fails the batch
-    const HaloHdr* h = kok ? C.hdr + kk : nullptr;
-    const int old = kok ? halo_old(*h, C.stamp) : 0;
-    const int64_t* hp = kok ? C.pos + (2 * int64_t(kk) + old) * C.km1 : nullptr;
+    const HaloRow H(C, kk);
     int64_t j = i;
     if (moff) {
       const int64_t a = C.gpos[last] - C.base;
@@ -850,10 +757,7 @@ __global__ __launch_bounds__(256) void stencil_deliver(const int32_t* __restrict
     }
     const bool host = j < host_cap;
     int64_t* p = host ? hpos + j * k : dpos + j * k;
-    for (int s = 0; s < k; s++) {
-      const int32_t r = out[i * k + s];
-      p[s] = r >= 0 ? halo_gpos(C, r) : (r == -1 || !kok ? -1 : hp[h->cnt[old] - (-r - 1)]);
-    }
+    for (int s = 0; s < k; s++) p[s] = H.pos(C, out[i * k + s]);
     if (host) hkey[j] = kk;
     else dkey[j] = kk;
   }

@@ -1,8 +1,8 @@
-// stencil_kernel.h -- the streaming stencil / chain kernel and its per-K launchers, shared by
-// stencil.hip (scan, gather, post-processing) and the per-K instantiation units stencil_k<N>.hip
-// (one translation unit per K, so the variants compile in parallel).
+// stencil_kernel.h -- the two streaming stencil kernels (count step) and their per-K launchers, shared
+// by stencil.hip (the finish step: scan, rows, delivery, post-processing) and the per-K instantiation
+// units stencil_k<N>.hip (one translation unit per K, so the variants compile in parallel).
 #pragma once
-// stencil.hip — strict-contiguity, single-cardinality fast path.
+// The strict-contiguity, single-cardinality fast path.
 //
 // For a pattern P1 -> ... -> Pk whose stages are all strict, cardinality ONE,
 // not optional, fold-free and distinctly named, the reference NFA
@@ -14,25 +14,26 @@
 // HBM-bound integer streaming: 4/8 B value per record in (plus 4 B key per record for the keyed
 // and carry kernels; the plain kernel without carry reads keys only where the stage predicates
 // already hold over a whole window, window_same_keys below: ~0.3 B per record in C2), 4*k B per
-// match out, one pass, ordered output:
-//   * 256-thread workgroups each own a super-tile of ST_SUB x 4096 records;
-//     no workgroup ever waits on another (no dequeue atomic, no look-back: a
-//     returning atomic per workgroup cost ~20% of the kernel, measured);
-//   * count phase, per 4096-record tile: lane-contiguous 16-B non-temporal
-//     loads (the next tile is in flight while this one is scanned), stage
-//     bitmask per record from an interval table, keys + masks staged in LDS
-//     with a halo carried over from the previous tile, 16 consecutive records
-//     per thread tested in registers, block scan;
-//   * write phase: each tile's matches compacted in LDS and written as one
-//     coalesced run into the super-tile's own slot (at s * 16384 * k ints),
-//     with the super-tile's count;
-//   * then an exclusive scan of those counts and stencil_gather move the
-//     slots into one contiguous output in record order (matches are sparse:
-//     ~2% of records in C2, so this touches ~2 x 18 MB against 800 MB read).
-//     The plain kernel without carry also stores each super-tile's count as a
-//     16-bit word; for 1025..8192 super-tiles (C2: 6104) one launch does both,
-//     stencil.hip stencil_finish_dense: every workgroup sums the 16-bit counts
-//     before its super-tiles itself and writes their rows.
+// match out, one pass, ordered output.  256-thread workgroups each own a super-tile of SUB x 4096
+// records (stencil_sub); no workgroup ever waits on another (no dequeue atomic, no look-back: a
+// returning atomic per workgroup cost ~20% of the kernel, measured).  Per 4096-record tile:
+// lane-contiguous 16-B non-temporal loads (the next tile is in flight while this one is scanned), a
+// stage bitmask per record from an interval table, 16 consecutive records per thread tested
+// against their window, a block scan of the threads' match counts.  A match leaves the kernel as ONE
+// int in the super-tile's slot, plus the super-tile's count; the finish step (stencil.hip, chosen by
+// the number of super-tiles) turns slots and counts into k-int rows, contiguous and in record order
+// (matches are sparse: ~2% of records in C2, so this touches ~2 x 18 MB against 800 MB read).
+//   * stencil_kernel, the keyed kernel (chain patterns, k = 8, KCEP_STENCIL_KEYED=1; with or without
+//     carry): keys and masks staged in LDS with a halo carried over from the previous tile.  All
+//     tiles are counted first; then each thread stores its own matches at their place in the
+//     super-tile's own slot (at tile0 * 4096 * K ints): the completing record, and an aux byte per
+//     match after the slot's SUB x 4096 ints (stencil_row).
+//   * stencil_plain_kernel (strict patterns, K <= 7): one byte of LDS per record and no keys there.
+//     Without carry it reads keys only at candidate windows (window_same_keys), stages the
+//     super-tile's matches (first records) in LDS and stores them as one run into the dense region
+//     (launch.h ST_DENSE), with the count also as a 16-bit word for stencil_finish_dense.  With
+//     carry each thread stores its matches per tile into the super-tile's own slot, boundary matches
+//     as -(1 + completing record) with an aux byte.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -658,23 +659,13 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
   // each thread stores its own matches at their place in the tile's run (record order; per record
   // oldest start first): no compaction through LDS, no barrier.  One int per match (its completing
   // record) plus one aux byte (chain: start distance | consumed stages << 2 | halo records << 6;
-  // carry: the stages taken from the halo) after the super-tile's SUB x 4096 ints; stencil_gather
-  // writes the K-int rows (stencil_row)
-  // without carry, a super-tile of at most ST_DENSE_KEYED matches writes them to the dense regions
-  // (launch.h; uniform per workgroup), a larger one to its own region after them
-  constexpr bool KD = !CARRY && ST_KEYED_DENSE;
-  const int64_t nsup = gridDim.x;
-  int64_t stot = 0;
-#pragma unroll
-  for (int j = 0; j < SUB; j++) stot += total[j];
-  const bool dense = KD && stot <= ST_DENSE_KEYED;
-  int32_t* const own = out + (KD ? nsup * (ST_DENSE_KEYED + ST_DENSE_KEYED / 4) : 0) + tile0 * int64_t(ST_TILE) * K;
-  int32_t* const slot = dense ? out + int64_t(s_super) * ST_DENSE_KEYED : own;
-  uint8_t* const aux = dense ? reinterpret_cast<uint8_t*>(out + nsup * ST_DENSE_KEYED) + int64_t(s_super) * ST_DENSE_KEYED
-                             : reinterpret_cast<uint8_t*>(own + SUB * ST_TILE);
+  // carry: the stages taken from the halo) after the super-tile's SUB x 4096 ints; the finish step
+  // (stencil.hip) writes the K-int rows (stencil_row)
+  int32_t* const slot = out + tile0 * int64_t(ST_TILE) * K;
+  uint8_t* const aux = reinterpret_cast<uint8_t*>(slot + SUB * ST_TILE);
   auto store_match = [&](int64_t m, int32_t v, uint8_t a) {
     slot[m] = v;
-    if constexpr (K > 1) aux[m] = a;             // (k = 1: the own region has no room after the ints; never read)
+    if constexpr (K > 1) aux[m] = a;             // (k = 1: the slot has no room after the ints; never read)
   };
   int64_t mbase = 0;                               // matches of the super-tile's earlier tiles
   if constexpr (CHAIN && CARRY) {                  // halo runs can exceed a tile's match space: fail the batch
@@ -876,9 +867,6 @@ __device__ __forceinline__ uint32_t window_same_keys(const int32_t* __restrict__
   return S;
 }
 
-#ifndef ST_PLAIN_EARLY
-#define ST_PLAIN_EARLY 1                         // next tile's loads issued before the image barrier (A/B knob)
-#endif
 #ifndef ST_PLAIN_WAVES
 #define ST_PLAIN_WAVES 6                          // waves per SIMD the register budget is cut for (A/B knob)
 #endif
@@ -892,17 +880,7 @@ __device__ __forceinline__ uint32_t window_same_keys(const int32_t* __restrict__
 // sparse LDS key image: the loader stores the key of each record that starts or ends a segment
 // (and of every record whose neighbour lies in another lane), the only keys a visit reads.  A
 // boundary match is stored as -(1 + completing record) with its halo record count in the slot's
-// aux byte (stencil_gather writes the -(1 + d) halo entries); an interior one as its first record.
-#ifndef ST_PLAIN_STAGE
-#define ST_PLAIN_STAGE 1                          // the super-tile's matches staged in LDS, one store run (A/B knob)
-#endif
-#ifndef ST_PLAIN_NTSTORE
-#define ST_PLAIN_NTSTORE 1                        // the staged run stored non-temporally (A/B knob)
-#endif
-#ifndef ST_PLAIN_PROBE
-#define ST_PLAIN_PROBE 0                          // timing probes (A/B builds only): 1 no match stores, 2 per-wave runs,
-                                                  // 3 no match stores with barrier (B) kept
-#endif
+// aux byte (the finish step writes the -(1 + d) halo entries); an interior one as its first record.
 #ifndef ST_CARRY_WAVES
 #define ST_CARRY_WAVES 4                          // waves per SIMD the carry variant's registers are cut for
 #endif
@@ -923,8 +901,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   __shared__ uint8_t s_tab[64];
   __shared__ uint8_t s_lut[256];
   __shared__ uint8_t s_nan[4];
-  constexpr bool STAGE = !CARRY && ST_PLAIN_STAGE;
-  __shared__ int32_t s_out[STAGE ? ST_TILE : 1];   // staged matches of the super-tile (see the tile loop's end)
+  __shared__ int32_t s_out[CARRY ? 1 : ST_TILE];   // no carry: staged matches of the super-tile (see the tile loop's end)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
@@ -964,8 +941,8 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   int32_t* slot = out + tile0 * int64_t(ST_TILE) * K;
   uint8_t* const aux = reinterpret_cast<uint8_t*>(slot + SUB * ST_TILE);   // carry: per match, after the ints
   int64_t sum = 0;
-  int nbuf = 0;                                   // STAGE: the first nbuf matches are staged in s_out (uniform)
-  // STAGE: the slot layout of launch.h ST_DENSE (the first matches in the dense region)
+  int nbuf = 0;                                   // no carry: the first nbuf matches are staged in s_out (uniform)
+  // no carry: the slot layout of launch.h ST_DENSE (the first matches in the dense region)
   int32_t* const dense = out + int64_t(blockIdx.x) * ST_DENSE;
   int32_t* const over = out + int64_t(gridDim.x) * ST_DENSE + tile0 * ST_TILE;
   for (int j = 0; j < ntl; j++) {                 // uniform
@@ -1008,13 +985,8 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
       if (j == 0 && tid == 0) s_lastk[0][0] = before0;
     // the chunk is consumed: the next tile's loads go out before the barrier, so a wave whose data
     // came early does not hold its refill back until the slowest wave's has arrived
-#if ST_PLAIN_EARLY
     if (j + 1 < ntl) load_tile<VT, TOPIC, CARRY>(cur, key, val, topic, base + ST_TILE, n, tid);
-#endif
     __syncthreads();                              // (A) the tile's image
-#if !ST_PLAIN_EARLY
-    if (j + 1 < ntl) load_tile<VT, TOPIC, CARRY>(cur, key, val, topic, base + ST_TILE, n, tid);   // prefetch
-#endif
 
     const int lb = ST_EPT * tid + 8;              // LDS byte of window record 0 (tile record 16 tid - 8)
     uint64_t m8[3];
@@ -1144,22 +1116,6 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
       before += int(__builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u))) << b;
       wtot += __popcll(m) << b;
     }
-#if ST_PLAIN_PROBE == 1 || ST_PLAIN_PROBE == 2
-    if constexpr (!CARRY) {                       // timing probes only (wrong output order / no output)
-      if (halo_lane) h_mask = s_mask[ST_TILE + tid];
-      if (ST_PLAIN_PROBE == 2) {
-        int32_t* ws = out + tile0 * int64_t(ST_TILE) * K + j * ST_TILE + wid * 1024 + before;
-        const int32_t b32 = int32_t(base) - (K - 1);
-        while (hit) {
-          const int i = __ffs(hit) - 1;
-          hit &= hit - 1;
-          *ws++ = b32 + tid * ST_EPT + i;
-        }
-      }
-      sum += wtot;
-      continue;
-    }
-#endif
     if (lane == 0) s_wsum[j & 1][wid] = wtot;
     if (halo_lane) h_mask = s_mask[ST_TILE + tid];   // the next tile's halo: this tile's last records
     if constexpr (CARRY)
@@ -1174,7 +1130,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
     }
     tot = __builtin_amdgcn_readfirstlane(tot);
     const int32_t b32 = int32_t(base) - (K - 1);  // record index < 2^31 (checked by the launcher)
-    if constexpr (STAGE) {
+    if constexpr (!CARRY) {
       // the super-tile's matches are staged in LDS and stored once, as one run into the dense region
       // (launch.h ST_DENSE): C2 kernel 139 -> 131 us; storing each tile's run into the
       // super-tile's own region (196 KB apart) cost 16 us over no stores at all, with or without the
@@ -1182,10 +1138,6 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
       // A tile whose matches no longer fit (over a quarter of the super-tile's records matching)
       // stores them straight to their place, and so do the later ones (sum only grows).
       const int p0 = int(sum) + o;
-      if (ST_PLAIN_PROBE == 3) {                  // timing probe: barrier (B) kept, no stores
-        sum += tot;
-        continue;
-      }
       if (sum + tot <= ST_TILE) {                 // uniform
         for (int q = 0; hit; q++) {
           const int i = __ffs(hit) - 1;
@@ -1204,43 +1156,33 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
       sum += tot;
       continue;
     }
-    // each thread stores its own matches at their place in the tile's run of the slot (no LDS
-    // compaction and no third barrier: L2 merges the run's lines; 147.7-150.2 vs 150.8-152.1 us,
-    // profiles/r03_ab_stencil_direct_store.jsonl).  ONE int per match -- its first record: the
-    // stages' records are consecutive here, so stencil_gather expands them to the K-int output
-    while (hit) {
-      const int i = __ffs(hit) - 1;
-      hit &= hit - 1;
-      if constexpr (CARRY) {
-        const uint32_t need = uint32_t(bneed >> (4 * i)) & 0xFu;
-        if (need) {                               // a boundary match: -(1 + completing record), halo count in aux
-          slot[o] = -(1 + int32_t(base) + tid * ST_EPT + i);
-          aux[sum + o] = uint8_t(need);
-          o++;
-          continue;
+    if constexpr (CARRY) {
+      // the carry variant only: each thread stores its own matches at their place in the tile's run
+      // of the super-tile's own slot (no LDS staging, no third barrier: L2 merges the run's lines).
+      // ONE int per match -- its first record: the stages' records are consecutive here, so the
+      // finish step expands them to the K-int output
+      while (hit) {
+        const int i = __ffs(hit) - 1;
+        hit &= hit - 1;
+        {                                         // a boundary match: -(1 + completing record), halo count in aux
+          const uint32_t need = uint32_t(bneed >> (4 * i)) & 0xFu;
+          if (need) {
+            slot[o] = -(1 + int32_t(base) + tid * ST_EPT + i);
+            aux[sum + o] = uint8_t(need);
+            o++;
+            continue;
+          }
         }
+        slot[o++] = b32 + tid * ST_EPT + i;
       }
-      slot[o++] = b32 + tid * ST_EPT + i;
+      slot += tot;
+      sum += tot;
     }
-    slot += tot;
-    sum += tot;
   }
-  if constexpr (STAGE) {
-    __syncthreads();                              // the last tile's staged matches
-#if ST_PLAIN_NTSTORE
-    for (int i = tid; i < nbuf; i += ST_THREADS) __builtin_nontemporal_store(s_out[i], &(i < ST_DENSE ? dense : over)[i]);
-#else
-    for (int i = tid; i < nbuf; i += ST_THREADS) (i < ST_DENSE ? dense : over)[i] = s_out[i];
-#endif
-  }
-#if ST_PLAIN_PROBE == 1 || ST_PLAIN_PROBE == 2
   if constexpr (!CARRY) {
-    if (lane == 0) s_wsum[0][wid] = int(sum);
-    __syncthreads();
-    if (tid == 0) tile_count[blockIdx.x] = s_wsum[0][0] + s_wsum[0][1] + s_wsum[0][2] + s_wsum[0][3];
-    return;
+    __syncthreads();                              // the last tile's staged matches
+    for (int i = tid; i < nbuf; i += ST_THREADS) __builtin_nontemporal_store(s_out[i], &(i < ST_DENSE ? dense : over)[i]);
   }
-#endif
   if (tid == 0) {
     tile_count[blockIdx.x] = sum;
     if constexpr (!CARRY) tile_count16[blockIdx.x] = uint16_t(sum);   // for stencil_finish_dense (stencil.hip)
@@ -1291,5 +1233,15 @@ inline hipError_t launch_k(const StencilLaunch& L, hipStream_t st) {
     return L.use_topic ? launch_kt<K, int64_t, true, CH>(L, st) : launch_kt<K, int64_t, false, CH>(L, st);
   return L.use_topic ? launch_kt<K, double, true, CH>(L, st) : launch_kt<K, double, false, CH>(L, st);
 }
+
+// the count step for k = N, defined in stencil_k<N>.hip and called by stencil.hip
+hipError_t stencil_count_k1(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k2(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k3(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k4(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k5(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k6(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k7(const StencilLaunch& L, hipStream_t st);
+hipError_t stencil_count_k8(const StencilLaunch& L, hipStream_t st);
 
 }  // namespace kcep

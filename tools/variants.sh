@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libkcep.so variants that differ in compile-time knobs of ONE translation unit, linked with
 # the other objects of the in-tree build, as build_variants/<name>/libkcep.so (A/B with KCEP_LIB=...).
-# Usage: tools/variants.sh UNIT[,UNIT...] "name:flags" ...   e.g. tools/variants.sh stencil_k3 "late:-DST_PLAIN_EARLY=0"
+# Usage: tools/variants.sh UNIT[,UNIT...] "name:flags" ...   e.g. tools/variants.sh stencil_k3 "w7:-DST_PLAIN_WAVES=7"
 set -e
 cd "$(dirname "$0")/.."
 make -s -C kafkastreams-cep_amd -j8 >/dev/null
