@@ -303,11 +303,11 @@ int cep_batch_errors(const cep_session* s, int64_t* records, int32_t* codes, int
    in the batch's result does.  CEP_E_UNSUPPORTED after a batch of another path. */
 int cep_batch_stopped(const cep_session* s, int64_t* keys, int64_t* records);
 /* CEP_SESSION_PROFILE sessions, after a general-path batch: per key segment {key id, live-run
-   high-water mark, run evaluations, kernel wall clock (100 MHz ticks), then shader clocks spent in
-   NFA.evaluate / edge predicates / buffer put+branch / removePattern / matchConstruction /
-   getPointerByVersion scans / predecessor appends / Dewey version copies, then counts of scans /
-   predecessor entries examined / digit-by-digit version checks (-1 each when the session runs the
-   built-in kernel), then the key's start (wall clock, 100 MHz ticks), the workspace words the key took (wave scratch region + device
+   high-water mark, run evaluations, kernel wall clock (100 MHz ticks), then 11 words of shader clocks
+   per phase of the wave kernel's record loop -- record setup / evaluation rounds / buffer commit / run
+   numbering / matchConstruction / admission / event-only predicates / round setup / record end, one
+   unused, queue placement (-1 each when the session runs the built-in kernel or the lane kernel,
+   which has no phase clocks), then the key's start (wall clock, 100 MHz ticks), the workspace words the key took (wave scratch region + device
    pool), then those words per allocation kind -- first workspace, match output, heap, run queues,
    private run lists / logs, aggregates, other -- and the device pool's share of them (-1 each when the
    session runs the built-in kernel)}; 25 int64 per key;

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "launch.h"
+#include "scan_dev.h"
 
 namespace kcep {
 
@@ -186,24 +187,10 @@ __global__ __launch_bounds__(256) void filter_scan(FilterArgs A, int64_t nt) {
 __device__ __forceinline__ void filter_emit(const FilterArgs& A, const bool (&adm)[FPT], int64_t b0, int64_t n,
                                             int* s_c) {
   static_assert(FPT == 4, "a thread's slots are one 8-byte store");
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int c = 0;
+  int c = 0, tot;
 #pragma unroll
   for (int j = 0; j < FPT; j++) c += adm[j] ? 1 : 0;
-  int incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_c[wid] = incl;
-  __syncthreads();
-  int run = incl - c, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    if (w < wid) run += s_c[w];
-    tot += s_c[w];
-  }
+  int run = block_scan_total<4>(c, s_c, threadIdx.x & 63, threadIdx.x >> 6, tot);
   uint64_t word = 0;
 #pragma unroll
   for (int j = 0; j < FPT; j++) {
@@ -289,21 +276,8 @@ __global__ __launch_bounds__(256) void filter_offsets(FilterArgs A, int64_t nt) 
   for (int64_t base = 0; base < nt; base += 256) {
     const int64_t i = base + threadIdx.x;
     const int64_t c = A.tile_cnt[i < nt ? i : nt - 1];
-    const int64_t v = i < nt ? c : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t y = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    int64_t run = carry + incl - v, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      if (w < wid) run += s_w[w];
-      tot += s_w[w];
-    }
+    int64_t tot;
+    const int64_t run = carry + block_scan_total<4>(i < nt ? c : 0, s_w, lane, wid, tot);
     if (i < nt) A.tile_off[i] = run;
     carry += tot;
     __syncthreads();

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "launch.h"
+#include "scan_dev.h"
 
 namespace kcep {
 
@@ -179,23 +180,11 @@ __global__ __launch_bounds__(256) void group_nodes(int64_t cap, const int32_t* _
   }
   __shared__ int64_t s_w[4];
   __shared__ unsigned long long s_base;
-  const int wid = threadIdx.x >> 6;
-  int64_t v = leader ? total : 0, incl = v;      // the workgroup's leaders' groups: one cursor add
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) s_w[wid] = incl;
+  int64_t sum;                                   // the workgroup's leaders' groups: one cursor add
+  const int64_t before = block_scan_total<4>(leader ? total : int64_t(0), s_w, lane, threadIdx.x >> 6, sum);
+  if (threadIdx.x == 0) s_base = sum ? atomicAdd(cursor, (unsigned long long)sum) : 0;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int64_t sum = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    s_base = sum ? atomicAdd(cursor, (unsigned long long)sum) : 0;
-  }
-  __syncthreads();
-  int64_t before = int64_t(s_base);
-  for (int w = 0; w < wid; w++) before += s_w[w];
-  if (leader) start[x] = before + incl - v;
+  if (leader) start[x] = int64_t(s_base) + before;
 }
 
 // grouped record g = start(leader) + prefix + rank <- arrival record i; zeroes the reorder's per-record counts

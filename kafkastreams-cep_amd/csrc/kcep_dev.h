@@ -63,10 +63,11 @@ constexpr int NFA_MAX_SL = 64;     // event-only edge predicates evaluated once 
 constexpr int NFA_STACK = 8;       // operand stack of the device interpreter (registers)
 constexpr int NFA_MAX_FRAMES = 16; // NFA.evaluate recursion depth of the device kernel
 constexpr int RUNS_MAX_STATES = 8; // aggregate registers of one deterministic run
-// per key segment: live-run max, run evaluations, wall clock (100 MHz), then (profiling kernels; -1
-// otherwise) shader clocks in evaluate / predicates / buffer put+branch / removePattern /
-// matchConstruction / first_compatible / add_pred / version copies, and counts of first_compatible
-// calls / pred entries examined / digit-by-digit checks, reserved (0), the key's workspace words (wave
+// per key segment: live-run max, run evaluations, wall clock (100 MHz), then 11 words of the wave
+// kernel's record-loop phases (profiling wave kernels, nfa_wave.h KWP_*; -1 otherwise: the lane kernel
+// has no phase clocks) -- lane 0's shader clocks in record setup / evaluation rounds / buffer commit /
+// run numbering / matchConstruction / admission / event-only predicates / round setup / record end,
+// one unused (0), queue placement --, the key's start (wall clock), the key's workspace words (wave
 // scratch + pool), then (profiling kernels) those words per allocation kind -- first workspace, match
 // output, heap, run queues, private lists, aggregates, other (nfa_dev.h AK_*) -- and the batch pool's
 // share of them (the rest came from the wave's recycled scratch region)

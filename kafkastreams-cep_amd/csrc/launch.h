@@ -189,14 +189,19 @@ hipError_t stencil_resolve_launch(const int32_t* key, const int32_t* out, int k,
 hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k, const int64_t* total, int64_t out_cap,
                                   const StencilCarry& C, const DeliverArgs& D, hipStream_t st);
 
+// ---- scan.hip: the device utilities every path shares ----
+hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
+hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n, const int64_t* n_dev, int64_t* out0,
+                               int64_t* out1, int64_t* total0, int64_t* total1, int64_t* tmp, hipStream_t st);
+hipError_t nfa_segments(const int32_t* key, int64_t n, int64_t* flag, int64_t* idx, int64_t* seg_start, int64_t* nseg,
+                        int64_t* tmp, hipStream_t st);
+hipError_t set_words_launch(int64_t* w, int n, int at, int64_t v, hipStream_t st);
+hipError_t gather_words_launch(const int64_t* a, int na, const int64_t* b, int nb, int64_t* h, hipStream_t st);
+
 // ---- nfa.hip ----
 hipError_t nfa_launch(const NfaArgs& A, hipStream_t st, hipFunction_t jf);
 hipError_t nfa_wave_launch(const NfaArgs& A, int64_t grid, hipStream_t st, const JitModule* j);
 int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j, bool stop);
-hipError_t nfa_segments(const int32_t* key, int64_t n, int64_t* flag, int64_t* idx, int64_t* seg_start, int64_t* nseg,
-                        int64_t* tmp, hipStream_t st);
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
-hipError_t set_words_launch(int64_t* w, int n, int at, int64_t v, hipStream_t st);
 hipError_t nfa_order_launch(const NfaArgs& A, int64_t nseg, uint8_t* bits, unsigned* bcnt, int32_t* order,
                             hipStream_t st, const JitModule* j, int lo);
 // The schedule's estimate buckets (log2 of the segment weight) below this one keep arrival order
@@ -205,9 +210,6 @@ hipError_t nfa_order_launch(const NfaArgs& A, int64_t nseg, uint8_t* bits, unsig
 // bucket 0 / 4 / 6 / 8 / 10: kernel 4.240 / 4.255 / 4.282 / 4.273 / 4.573 ms, kcep_nfa_wave
 // 201.2 / 201.3 / 200.9 / 197.6 / 183.0 MB per launch; profiles/r05_c4_order_lo.txt)
 constexpr int NFA_ORDER_LO = 8;
-hipError_t gather_words_launch(const int64_t* a, int na, const int64_t* b, int nb, int64_t* h, hipStream_t st);
-hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n, const int64_t* n_dev, int64_t* out0,
-                               int64_t* out1, int64_t* total0, int64_t* total1, int64_t* tmp, hipStream_t st);
 hipError_t nfa_compact_launch(int64_t nseg, const int64_t* nseg_dev, int64_t nm, int64_t ne, const int64_t* tot_dev,
                               const int32_t* key, const int64_t* seg_start, const int64_t* res_out, const int64_t* res_ent,
                               const int64_t* moff, const int64_t* eoff, int64_t* match_record, int32_t* match_key,

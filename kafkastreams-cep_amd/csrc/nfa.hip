@@ -39,8 +39,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/kcep.h"
 #include "launch.h"
 #include "interp.h"
@@ -63,179 +61,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void nf
   nfa_wave_body<AGG, STOP>(A);
 }
 
-// ---- segments, scans, output compaction, carry commit ----
-// Key segments of a grouped batch in three passes over 1024-record blocks: boundaries per block, the
-// blocks' exclusive prefix (scan_sums_reg), then every boundary's segment start.  flag / idx (optional:
-// the runs carry build reads them) get the per-record boundary flag and its exclusive prefix.
-__device__ __forceinline__ int64_t block_excl_256(int64_t v, int64_t* s, int64_t& total) {
-  s[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int64_t y = threadIdx.x >= unsigned(d) ? s[threadIdx.x - d] : 0;
-    __syncthreads();
-    s[threadIdx.x] += y;
-    __syncthreads();
-  }
-  total = s[255];
-  return s[threadIdx.x] - v;
-}
-__global__ void seg_count(const int32_t* __restrict__ key, int64_t n, int64_t* __restrict__ bsum) {
-  __shared__ int64_t s[256];
-  const int64_t b0 = int64_t(blockIdx.x) * 1024 + threadIdx.x * 4;
-  int64_t acc = 0;
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + k;
-    if (i < n) acc += (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
-  }
-  int64_t tot = 0;
-  block_excl_256(acc, s, tot);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ void seg_write(const int32_t* __restrict__ key, int64_t n, const int64_t* __restrict__ boff,
-                          const int64_t* __restrict__ nseg, int64_t* __restrict__ seg_start, int64_t* __restrict__ flag,
-                          int64_t* __restrict__ idx) {
-  __shared__ int64_t s[256];
-  const int64_t b0 = int64_t(blockIdx.x) * 1024 + threadIdx.x * 4;
-  int f[4], acc = 0;
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + k;
-    f[k] = i < n && (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
-    acc += f[k];
-  }
-  int64_t tot = 0;
-  int64_t run = boff[blockIdx.x] + block_excl_256(acc, s, tot);
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + k;
-    if (i >= n) break;
-    if (f[k]) seg_start[run] = i;
-    if (flag) { flag[i] = f[k]; idx[i] = run; }
-    run += f[k];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) seg_start[*nseg] = n;
-}
-
-// exclusive scans, 1024 elements per block: (1) block sums, (2) scan of block sums in one block,
-// (3) per-block scan + offset.  Two arrays of one length at once (blockIdx.y / the block of pass 2
-// picks the array; tmp holds 2 x the block count); n_dev (optional): the length on the device, at
-// most n (the grid is sized by n).
-struct ScanPair {
-  const int64_t* in[2];
-  int64_t* out[2];
-  int64_t* total[2];
-  int64_t n;
-  const int64_t* n_dev;
-  int64_t nb;                     // blocks of the grid (from n)
-};
-__device__ __forceinline__ int64_t scan_len(const ScanPair& S) {
-  return S.n_dev ? (*S.n_dev < S.n ? *S.n_dev : S.n) : S.n;
-}
-__global__ void scan_blocks(ScanPair S, int64_t* __restrict__ bsum) {
-  __shared__ int64_t s[256];
-  const int64_t n = scan_len(S);
-  const int64_t* __restrict__ in = S.in[blockIdx.y];
-  const int64_t b0 = int64_t(blockIdx.x) * 1024;
-  // loads at clamped indices, masked after (a load under `i < n` is a branch waited on inside it)
-  const int64_t last = n > 0 ? n - 1 : 0;
-  int64_t v[4], acc = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + threadIdx.x * 4 + k;
-    v[k] = in[i < n ? i : last];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) acc += b0 + threadIdx.x * 4 + k < n ? v[k] : 0;
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (threadIdx.x < unsigned(d)) s[threadIdx.x] += s[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bsum[blockIdx.y * S.nb + blockIdx.x] = s[0];
-}
-__global__ void scan_sums(int64_t* __restrict__ bsum, int64_t nb, int64_t* __restrict__ total) {
-  __shared__ int64_t s[256];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = i < nb ? bsum[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int64_t y = threadIdx.x >= unsigned(d) ? s[threadIdx.x - d] : 0;
-      __syncthreads();
-      s[threadIdx.x] += y;
-      __syncthreads();
-    }
-    if (i < nb) bsum[i] = carry + s[threadIdx.x] - v;
-    carry += s[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-// the same scan of up to 16 x 1024 block sums (batches of <= 16 M elements) in one pass: every
-// thread holds its 16 consecutive sums in registers, one wave-level and one block-level scan (the loop
-// above walks the sums 256 at a time, two barriers per step: 44 us for 10 M elements)
-constexpr int SCAN_REG = 16;
-__device__ __forceinline__ void scan_sums_reg_body(int64_t* __restrict__ bsum, int64_t nb, int64_t* __restrict__ total) {
-  __shared__ int64_t s_w[16];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int64_t per = (nb + 1023) / 1024, a = tid * per;
-  int64_t v[SCAN_REG], sum = 0;
-  const int64_t lastb = nb > 0 ? nb - 1 : 0;
-#pragma unroll
-  for (int i = 0; i < SCAN_REG; i++) v[i] = bsum[i < per && a + i < nb ? a + i : lastb];   // (clamped, masked below)
-#pragma unroll
-  for (int i = 0; i < SCAN_REG; i++) {
-    if (!(i < per && a + i < nb)) v[i] = 0;
-    sum += v[i];
-  }
-  int64_t incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  int64_t run = incl - sum;
-  for (int w = 0; w < wid; w++) run += s_w[w];
-#pragma unroll
-  for (int i = 0; i < SCAN_REG; i++)
-    if (i < per && a + i < nb) { bsum[a + i] = run; run += v[i]; }
-  if (tid == 1023) *total = run;
-}
-__global__ __launch_bounds__(1024) void scan_sums_reg(int64_t* __restrict__ bsum, int64_t nb, int64_t* __restrict__ total) {
-  scan_sums_reg_body(bsum, nb, total);
-}
-__global__ __launch_bounds__(1024) void scan_sums_pair(ScanPair S, int64_t* __restrict__ bsum) {
-  const int64_t nb = (scan_len(S) + 1023) / 1024;
-  scan_sums_reg_body(bsum + blockIdx.x * S.nb, nb, S.total[blockIdx.x]);
-}
-__global__ void scan_final(ScanPair S, const int64_t* __restrict__ bsum) {
-  __shared__ int64_t s[256];
-  const int64_t n = scan_len(S);
-  const int64_t* __restrict__ in = S.in[blockIdx.y];
-  int64_t* __restrict__ out = S.out[blockIdx.y];
-  const int64_t b0 = int64_t(blockIdx.x) * 1024;
-  if (b0 >= n) return;                             // (whole block: the barriers below stay uniform)
-  int64_t v[4], acc = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + threadIdx.x * 4 + k;
-    v[k] = in[i < n ? i : n - 1];                  // (clamped, masked below; n > b0 >= 0 here)
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    if (b0 + threadIdx.x * 4 + k >= n) v[k] = 0;
-    acc += v[k];
-  }
-  int64_t tot = 0;
-  int64_t run = bsum[blockIdx.y * S.nb + blockIdx.x] + block_excl_256(acc, s, tot);
-  for (int k = 0; k < 4; k++) {
-    const int64_t i = b0 + threadIdx.x * 4 + k;
-    if (i < n) out[i] = run;
-    run += v[k];
-  }
+// The built-in kernels by their template flags (all of one type, so the choice is a pointer)
+using NfaKernel = void (*)(NfaArgs);
+static NfaKernel lane_kernel(bool stop) { return stop ? nfa_kernel<true> : nfa_kernel<false>; }
+static NfaKernel wave_kernel(bool agg, bool stop) {
+  return agg ? (stop ? nfa_wave_kernel<true, true> : nfa_wave_kernel<true, false>)
+             : (stop ? nfa_wave_kernel<false, true> : nfa_wave_kernel<false, false>);
 }
 
 // jf: the pattern's compiled nfa kernel (jit.cpp; its STOP build when A.stop_at is set), nullptr for the
@@ -249,8 +80,7 @@ hipError_t nfa_launch(const NfaArgs& A, hipStream_t st, hipFunction_t jf) {
     void* args[] = {&a};
     return hipModuleLaunchKernel(jf, grid, 1, 1, 64, 1, 1, 0, st, args, nullptr);
   }
-  if (A.stop_at) hipLaunchKernelGGL(nfa_kernel<true>, dim3(grid), dim3(64), 0, st, A);
-  else hipLaunchKernelGGL(nfa_kernel<false>, dim3(grid), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(lane_kernel(A.stop_at != nullptr), dim3(grid), dim3(64), 0, st, A);
   return hipGetLastError();
 }
 
@@ -373,10 +203,7 @@ hipError_t nfa_order_launch(const NfaArgs& A, int64_t nseg, uint8_t* bits, unsig
 int64_t nfa_wave_grid(int64_t nseg, bool agg, const JitModule* j, bool stop) {
   int per_cu = 0, cus = 0, dev = 0;
   hipError_t e = j ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, j->nfa_wave, 64, 0)
-                 : agg ? (stop ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<true, true>, 64, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<true, false>, 64, 0))
-                       : (stop ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<false, true>, 64, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nfa_wave_kernel<false, false>, 64, 0));
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wave_kernel(agg, stop), 64, 0);
   if (e != hipSuccess || per_cu <= 0) per_cu = 12;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
       cus <= 0)
@@ -393,66 +220,11 @@ hipError_t nfa_wave_launch(const NfaArgs& A, int64_t grid, hipStream_t st, const
   NfaArgs a = A;
   void* args[] = {&a};
   if (j) return hipModuleLaunchKernel(j->nfa_wave, unsigned(grid), 1, 1, 64, 1, 1, 0, st, args, nullptr);
-  const dim3 g{unsigned(grid)}, b{64};
-  if (A.wave_agg && A.stop_at) hipLaunchKernelGGL((nfa_wave_kernel<true, true>), g, b, 0, st, A);
-  else if (A.wave_agg) hipLaunchKernelGGL((nfa_wave_kernel<true, false>), g, b, 0, st, A);
-  else if (A.stop_at) hipLaunchKernelGGL((nfa_wave_kernel<false, true>), g, b, 0, st, A);
-  else hipLaunchKernelGGL((nfa_wave_kernel<false, false>), g, b, 0, st, A);
+  hipLaunchKernelGGL(wave_kernel(A.wave_agg != 0, A.stop_at != nullptr), dim3(unsigned(grid)), dim3(64), 0, st, A);
   return hipGetLastError();
 }
 
-hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp,
-                          hipStream_t st) {
-  if (n <= 0) return hipMemsetAsync(total, 0, sizeof(int64_t), st);
-  const int64_t nb = (n + 1023) / 1024;
-  const ScanPair S{{in, in}, {out, out}, {total, total}, n, nullptr, nb};
-  hipLaunchKernelGGL(scan_blocks, dim3(unsigned(nb)), dim3(256), 0, st, S, tmp);
-  if (nb <= int64_t(SCAN_REG) * 1024) hipLaunchKernelGGL(scan_sums_reg, dim3(1), dim3(1024), 0, st, tmp, nb, total);
-  else hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, st, tmp, nb, total);
-  hipLaunchKernelGGL(scan_final, dim3(unsigned(nb)), dim3(256), 0, st, S, tmp);
-  return hipGetLastError();
-}
-
-// w[0..n) = 0 except w[at] = v
-__global__ void set_words(int64_t* __restrict__ w, int n, int at, int64_t v) {
-  const int t = threadIdx.x;
-  if (t < n) w[t] = t == at ? v : 0;
-}
-hipError_t set_words_launch(int64_t* w, int n, int at, int64_t v, hipStream_t st) {
-  if (n > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(set_words, dim3(1), dim3(64), 0, st, w, n, at, v);
-  return hipGetLastError();
-}
-// a[0..na) then b[0..nb) into h (pinned host memory mapped for the device): the host's view of a batch
-__global__ void gather_words(const int64_t* __restrict__ a, int na, const int64_t* __restrict__ b, int nb,
-                             int64_t* __restrict__ h) {
-  const int t = threadIdx.x;
-  if (t < na) h[t] = a[t];
-  else if (t < na + nb) h[t] = b[t - na];
-}
-hipError_t gather_words_launch(const int64_t* a, int na, const int64_t* b, int nb, int64_t* h, hipStream_t st) {
-  if (na + nb > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gather_words, dim3(1), dim3(64), 0, st, a, na, b, nb, h);
-  return hipGetLastError();
-}
-
-// Two exclusive scans of one length n (or *n_dev <= n, read on the device) in one set of launches;
-// tmp: 2 x ceil(n / 1024) words.
-hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n, const int64_t* n_dev, int64_t* out0,
-                               int64_t* out1, int64_t* total0, int64_t* total1, int64_t* tmp, hipStream_t st) {
-  const int64_t nb = (std::max<int64_t>(n, 1) + 1023) / 1024;
-  const ScanPair S{{in0, in1}, {out0, out1}, {total0, total1}, std::max<int64_t>(n, 0), n_dev, nb};
-  hipLaunchKernelGGL(scan_blocks, dim3(unsigned(nb), 2), dim3(256), 0, st, S, tmp);
-  if (nb <= int64_t(SCAN_REG) * 1024) {
-    hipLaunchKernelGGL(scan_sums_pair, dim3(2), dim3(1024), 0, st, S, tmp);
-  } else {                                         // (blocks past *n_dev summed to 0 in scan_blocks)
-    hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, st, tmp, nb, total0);
-    hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, st, tmp + nb, nb, total1);
-  }
-  hipLaunchKernelGGL(scan_final, dim3(unsigned(nb), 2), dim3(256), 0, st, S, tmp);
-  return hipGetLastError();
-}
-
+// ---- after the kernel: trim, output compaction, carry commit ----
 // CEP_BATCH_STOP_AT_ERROR: the batch as the reference leaves it when its task fails at the earliest
 // exception, stream position p* (NfaArgs.stop_at, final once the NFA kernel is done).  One thread per
 // segment: its matches are cut to those emitted at positions < p* (a key's headers are in emission
@@ -575,19 +347,6 @@ __global__ void carry_move(int64_t* __restrict__ ctab, int64_t nkeys, const int3
   const int32_t w = a[CB_WORDS];
   for (int32_t i = 0; i < w; i++) b[i] = a[i];
   ctab[k] = off[k];
-}
-
-// flag / idx: nullptr, or n words each (the runs carry build's per-record boundary flags); tmp:
-// ceil(n / 1024) + 1 words.  *nseg: the segment count (device).
-hipError_t nfa_segments(const int32_t* key, int64_t n, int64_t* flag, int64_t* idx, int64_t* seg_start, int64_t* nseg,
-                        int64_t* tmp, hipStream_t st) {
-  if (n <= 0) return hipMemsetAsync(nseg, 0, sizeof(int64_t), st);
-  const int64_t nb = (n + 1023) / 1024;
-  hipLaunchKernelGGL(seg_count, dim3(unsigned(nb)), dim3(256), 0, st, key, n, tmp);
-  if (nb <= int64_t(SCAN_REG) * 1024) hipLaunchKernelGGL(scan_sums_reg, dim3(1), dim3(1024), 0, st, tmp, nb, nseg);
-  else hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, st, tmp, nb, nseg);
-  hipLaunchKernelGGL(seg_write, dim3(unsigned(nb)), dim3(256), 0, st, key, n, tmp, nseg, seg_start, flag, idx);
-  return hipGetLastError();
 }
 
 hipError_t nfa_compact_launch(int64_t nseg, const int64_t* nseg_dev, int64_t nm, int64_t ne, const int64_t* tot_dev,

@@ -132,24 +132,7 @@ struct Lane {
   int32_t wgrow;               // wave: the shared heap was too small (grow it and re-run the round)
   int32_t ov_own;              // wave: this evaluation wrote an aggregate of its run's own sequence
   KeyAlloc* wpool;             // wave: the key's allocator, in LDS (every lane allocates for the key)
-#ifdef KCEP_PHASES_LANE
-  uint64_t ph[11];             // lane-engine profiling builds only: clocks in evaluate / predicates / buffer
-                               // puts+branch / removePattern / matchConstruction / first_compatible / add_pred /
-                               // versions, then counts: first_compatible calls / entries examined / digit checks
-#endif
 };
-
-// phase timers of the lane engine (KCEP_PHASES_LANE builds only: they share Lane.ph with the wave
-// kernel's record-loop timers, nfa_wave.h KWP_*, which the CEP_SESSION_PROFILE kernels keep)
-#ifdef KCEP_PHASES_LANE
-#define KPH_BEGIN(l, i) const uint64_t kph_t##i = clock64()
-#define KPH_END(l, i) const_cast<Lane&>(l).ph[i] += clock64() - kph_t##i
-#define KPH_COUNT(l, i, n) const_cast<Lane&>(l).ph[i] += (n)
-#else
-#define KPH_BEGIN(l, i)
-#define KPH_END(l, i)
-#define KPH_COUNT(l, i, n)
-#endif
 
 // ---- pool ----
 // every allocation is a multiple of 16 bytes (queues are read as int4)
@@ -269,8 +252,8 @@ __device__ __forceinline__ void dw_copy(int32_t* h, int dst, int src, int len) {
   }
   for (; i < len; i++) h[dst + i] = h[src + i];
 }
-template <bool W>
-__device__ __forceinline__ int dw_add_stage_(Lane& l, int v) {            // DeweyVersion.addStage :95-97
+template <bool W = false>
+__device__ __forceinline__ int dw_add_stage(Lane& l, int v) {             // DeweyVersion.addStage :95-97
   const int len = l.heap[v];
   const int n = heap_alloc<W>(l, len + 2);
   if (n < 0) return -1;
@@ -279,8 +262,8 @@ __device__ __forceinline__ int dw_add_stage_(Lane& l, int v) {            // Dew
   l.heap[n + 1 + len] = 0;
   return n;
 }
-template <bool W>
-__device__ __forceinline__ int dw_add_run_(Lane& l, int v, int off) {     // DeweyVersion.addRun :62-67
+template <bool W = false>
+__device__ __forceinline__ int dw_add_run(Lane& l, int v, int off) {      // DeweyVersion.addRun :62-67
   const int len = l.heap[v];
   const int idx = len - off;
   if (idx < 0 || idx >= len) { l.err = CEP_E_INDEX; return -1; }
@@ -290,20 +273,6 @@ __device__ __forceinline__ int dw_add_run_(Lane& l, int v, int off) {     // Dew
   l.heap[n] = len;
   dw_copy(l.heap, n + 1, v + 1, len);
   l.heap[n + 1 + idx] = bumped;
-  return n;
-}
-template <bool W = false>
-__device__ __forceinline__ int dw_add_stage(Lane& l, int v) {
-  KPH_BEGIN(l, 7);
-  const int n = dw_add_stage_<W>(l, v);
-  KPH_END(l, 7);
-  return n;
-}
-template <bool W = false>
-__device__ __forceinline__ int dw_add_run(Lane& l, int v, int off) {
-  KPH_BEGIN(l, 7);
-  const int n = dw_add_run_<W>(l, v, off);
-  KPH_END(l, 7);
   return n;
 }
 
@@ -330,7 +299,7 @@ __device__ __forceinline__ int32_t* node(Lane& l, int slot, int ev) {
 __device__ __forceinline__ int slot_of(const Lane& l, int sid) { return ST_SLOT(l, sid); }
 __device__ __forceinline__ bool exists(const int32_t* nd) { return nd[3] & NF_EXISTS; }
 
-__device__ __forceinline__ bool add_pred_(Lane& l, int32_t* nd, int ver, int pslot, int pev) {   // MatchedEvent.addPredecessor
+__device__ __forceinline__ bool add_pred(Lane& l, int32_t* nd, int ver, int pslot, int pev) {   // MatchedEvent.addPredecessor
   const int p = heap_alloc(l, PW);
   if (p < 0) return false;
   l.heap[p] = ver; l.heap[p + 1] = pslot; l.heap[p + 2] = pev; l.heap[p + 3] = -1;
@@ -339,12 +308,6 @@ __device__ __forceinline__ bool add_pred_(Lane& l, int32_t* nd, int ver, int psl
   else l.heap[nd[2] + 3] = p;
   nd[2] = p;
   return true;
-}
-__device__ __forceinline__ bool add_pred(Lane& l, int32_t* nd, int ver, int pslot, int pev) {
-  KPH_BEGIN(l, 6);
-  const bool ok = add_pred_(l, nd, ver, pslot, pev);
-  KPH_END(l, 6);
-  return ok;
 }
 // wave mode: a buffer operation is logged (WL words: kind | cur sid << 8 | prev sid << 16, event, prev
 // event, version) and applied in queue order after the round (nfa_wave.h)
@@ -380,21 +343,13 @@ __device__ __forceinline__ void buf_put3(Lane& l, int cur_sid, int ev, int ver) 
   c[0] = 1; c[1] = -1; c[2] = -1; c[3] = NF_EXISTS;
   add_pred(l, c, ver, -1, 0);
 }
-__device__ __forceinline__ int first_compatible_(const Lane& l, const int32_t* nd, int ver, int* prevp) {   // getPointerByVersion
+__device__ __forceinline__ int first_compatible(const Lane& l, const int32_t* nd, int ver, int* prevp) {   // getPointerByVersion
   int pp = -1;
   for (int p = nd[1]; p >= 0; p = l.heap[p + 3]) {
-    KPH_COUNT(l, 9, 1);
     if (dw_compatible(l, ver, l.heap[p], l.heap[p + 4], l.heap[p + 5])) { if (prevp) *prevp = pp; return p; }
     pp = p;
   }
   return -1;
-}
-__device__ __forceinline__ int first_compatible(const Lane& l, const int32_t* nd, int ver, int* prevp) {
-  KPH_BEGIN(l, 5);
-  const int p = first_compatible_(l, nd, ver, prevp);
-  KPH_END(l, 5);
-  KPH_COUNT(l, 8, 1);
-  return p;
 }
 // branch (:132-142)
 template <bool W = false>
@@ -862,9 +817,7 @@ __device__ __forceinline__ bool frame_enter(Lane& l, Frame& f, const Run& run) {
       } else {
         Ctx c{run.seq, f.prev_sid(), run.ev, f.ver, false, 0, 0};
         int64_t v;
-        KPH_BEGIN(l, 1);
         const bool good = run_code<W>(l, pc, c, v);
-        KPH_END(l, 1);
         if (!good) return false;
         ok = v != 0;
       }
@@ -924,17 +877,13 @@ __device__ __forceinline__ bool evaluate(Lane& l, const Run& run, Frame* fr) {
         if (!push_t(l, mk_run(cur, cur, ver, l.r, seq, false, false))) return false;
         int pv = ver;
         if (!(!f.flag(FB_BRANCHING) || f.flag(FB_IGNORED))) { pv = dw_add_run<W>(l, ver, 1); if (pv < 0) return false; }
-        KPH_BEGIN(l, 2);
         if (prev >= 0) buf_put5<W>(l, cur, l.r, prev, run.ev, pv);
         else buf_put3<W>(l, cur, l.r, pv);
-        KPH_END(l, 2);
         if (l.err || l.overflow) return false;
         f.set(FB_CONSUMED);
       } else if (op == E_BEGIN) {                                    // :256-271
-        KPH_BEGIN(l, 2);
         if (prev >= 0) buf_put5<W>(l, cur, l.r, prev, run.ev, ver);
         else buf_put3<W>(l, cur, l.r, ver);
-        KPH_END(l, 2);
         if (l.err || l.overflow) return false;
         if (!push_t(l, mk_run(cur, target, ver, l.r, seq, false, false))) return false;
         f.set(FB_CONSUMED);
@@ -965,9 +914,7 @@ __device__ __forceinline__ bool evaluate(Lane& l, const Run& run, Frame* fr) {
           if (t && !agg_write<W>(l, st, nseq, t, v)) return false;           // (a new sequence's row is null)
         }
         if (!pb) {
-          KPH_BEGIN(l, 2);
           buf_branch<W>(l, prev, pev, ver);
-          KPH_END(l, 2);
           if (l.err) return false;
         }
       } else if (!f.flag(FB_PROCEED)) {
@@ -1055,14 +1002,10 @@ __device__ __forceinline__ bool step(Lane& l, Frame* fr) {
     l.tlen = 0;
     // window check (:179-188): every non-begin run sits on an epsilon stage
     // whose window is -1, so it never prunes; nothing to evaluate.
-    KPH_BEGIN(l, 0);
     const bool good = evaluate(l, run, fr);
-    KPH_END(l, 0);
     if (!good) return false;
     if (l.tlen == 0) {                                               // removePattern :160-163
-      KPH_BEGIN(l, 3);
       const int rm = buf_peek(l, r_sid(run), run.ev, run.ver, true, nullptr, 0);
-      KPH_END(l, 3);
       if (rm < 0) return false;
     }
     for (int t = 0; t < l.tlen; t++) {
@@ -1084,9 +1027,7 @@ __device__ __forceinline__ bool step(Lane& l, Frame* fr) {
   l.qlen = qn;
   for (int k = 0; k < l.flen; k++) {                                // matchConstruction :151-158
     const int4 y = reinterpret_cast<int4*>(l.fq)[k];
-    KPH_BEGIN(l, 4);
     const bool good = emit_match(l, Run{y.x, y.y, y.z, y.w});
-    KPH_END(l, 4);
     if (!good) return false;
   }
   return true;
@@ -1469,9 +1410,7 @@ __device__ __forceinline__ void key_end(Lane& l, const NfaArgs& A, int seg, int6
     pr[0] = live_max;
     pr[1] = evals;
     pr[2] = int64_t(wall_clock64() - t0);
-#if defined(KCEP_PHASES_LANE)
-    for (int i = 0; i < 11; i++) pr[3 + i] = int64_t(l.ph[i]);
-#elif defined(KCEP_PHASES)
+#ifdef KCEP_PHASES
     for (int i = 0; i < 11; i++) pr[3 + i] = prof ? int64_t(prof->ph[i]) : -1;
 #else
     for (int i = 0; i < 11; i++) pr[3 + i] = -1;
@@ -1520,9 +1459,6 @@ __device__ __forceinline__ void nfa_kernel_body(const NfaArgs& A) {
   Frame fr[MAXD];
   int64_t err_rec = -1;
   const bool proc = A.mode == CEP_MODE_PROCESSOR;
-#ifdef KCEP_PHASES_LANE
-  for (int i = 0; i < 11; i++) l.ph[i] = 0;
-#endif
   int32_t live_max = l.qlen;                                         // live-run high-water mark of the key
   int64_t evals = 0;
   const uint64_t t0 = A.profile ? wall_clock64() : 0;

@@ -31,6 +31,7 @@
 #include "launch.h"
 #include "interp.h"
 #include "runs_dev.h"
+#include "scan_dev.h"
 
 namespace kcep {
 
@@ -61,16 +62,7 @@ __global__ __launch_bounds__(256) void runs_compact(const int32_t* __restrict__ 
     if (q < ipt && a + q < c1) e[q] = end_of[a + q];
     cnt += e[q] >= 0;
   }
-  int inc = cnt;                                    // inclusive scan over the wave
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(inc, d, 64);
-    if ((threadIdx.x & 63) >= d) inc += y;
-  }
-  if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  int64_t at = pre[blockIdx.x] + inc - cnt;
-  for (int w = 0; w < int(threadIdx.x >> 6); w++) at += s_w[w];
+  int64_t at = pre[blockIdx.x] + block_scan_excl(cnt, s_w, threadIdx.x & 63, threadIdx.x >> 6);
 #pragma unroll
   for (int q = 0; q < 4; q++)
     if (e[q] >= 0) out[at++] = (unsigned long long)(int64_t(e[q]) << 31 | (a + q));
@@ -114,16 +106,7 @@ __global__ __launch_bounds__(1024) void runs_chunk_scan(const int64_t* __restric
       l += chunk_stat<by_end>(stat, W, 1, w);
     }
   }
-  int64_t ic = c, il = l;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t yc = __shfl_up(ic, d, 64), yl = __shfl_up(il, d, 64);
-    if (lane >= d) { ic += yc; il += yl; }
-  }
-  if (lane == 63) { s_c[wv] = ic; s_l[wv] = il; }
-  __syncthreads();
-  int64_t oc = ic - c, ol = il - l;
-  for (int q = 0; q < wv; q++) { oc += s_c[q]; ol += s_l[q]; }
+  int64_t oc = block_scan_excl(c, s_c, lane, wv), ol = block_scan_excl(l, s_l, lane, wv);
   if (per <= REG) {
 #pragma unroll
     for (int q = 0; q < REG; q++)
@@ -141,11 +124,9 @@ __global__ __launch_bounds__(1024) void runs_chunk_scan(const int64_t* __restric
       ol += chunk_stat<by_end>(stat, W, 1, w);
     }
   }
-  if (threadIdx.x == 1023) {
-    int64_t tc = 0, tl = 0;
-    for (int q = 0; q < 16; q++) { tc += s_c[q]; tl += s_l[q]; }
-    *tot_cnt = tc;
-    *tot_len = tl;
+  if (threadIdx.x == 1023) {                       // (the last thread ends at the totals)
+    *tot_cnt = oc;
+    *tot_len = ol;
   }
 }
 
@@ -280,9 +261,6 @@ __global__ __launch_bounds__(256) void runs_expand(const DevProgram* __restrict_
 // contiguous entry range, each entry's stage from its run's packed segments.  Replaces runs_compact +
 // runs_order + the entry-offset scan + runs_expand (one pass over end_of and the segments instead of a
 // start-ordered list, a sorted copy, a length array and gathers at start positions).
-#ifndef RUNS_EMIT_PROBE
-#define RUNS_EMIT_PROBE 0                          // timing probes (A/B builds only): 1 no output, 2 headers only
-#endif
 constexpr int RUNS_EMIT_MAX = 2 * RUNS_CHUNK;      // window of starts: chunk + span < 2 chunks
 constexpr int EMIT_T = 2048;                       // entries per pass of the entry phase (8 per thread)
 static_assert(RUNS_EMIT_MAX <= 65536, "run indices are 16-bit in the entry phase");
@@ -346,17 +324,8 @@ __global__ __launch_bounds__(256) void runs_emit(const DevProgram* __restrict__ 
     v[q] = x < E ? s_cnt[x] : 0;
     acc += v[q];
   }
-  int inc = acc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(inc, d, 64);
-    if ((tid & 63) >= d) inc += y;
-  }
-  if ((tid & 63) == 63) s_w[tid >> 6] = inc;
-  __syncthreads();
-  int run = inc - acc;
-  for (int w = 0; w < (tid >> 6); w++) run += s_w[w];
-  const int M = s_w[0] + s_w[1] + s_w[2] + s_w[3];  // the chunk's runs
+  int M;                                           // the chunk's runs
+  int run = block_scan_total<4>(acc, s_w, tid & 63, tid >> 6, M);
 #pragma unroll
   for (int q = 0; q < 4; q++) {                    // (each thread rewrites only the counts it read)
     const int x = 4 * tid + q;
@@ -387,17 +356,8 @@ __global__ __launch_bounds__(256) void runs_emit(const DevProgram* __restrict__ 
     const int32_t r = s_run[i];
     lens += int(c0 - lo) + (r >> 11) - (r & 2047) + 1;
   }
-  inc = lens;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(inc, d, 64);
-    if ((tid & 63) >= d) inc += y;
-  }
-  if ((tid & 63) == 63) s_w[tid >> 6] = inc;     // (s_w's first use was read before the last barrier)
-  __syncthreads();
-  run = inc - lens;
-  for (int w = 0; w < (tid >> 6); w++) run += s_w[w];
-  const int NE = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  int NE;                                          // (s_w's first use was read before the last barrier)
+  run = block_scan_total<4>(lens, s_w, tid & 63, tid >> 6, NE);
   for (int i = R * tid; i < R * tid + R && i < M; i++) {
     s_at[i] = run;
     const int32_t r = s_run[i];
@@ -405,7 +365,6 @@ __global__ __launch_bounds__(256) void runs_emit(const DevProgram* __restrict__ 
   }
   if (tid == 0) s_at[M] = NE;
   __syncthreads();
-  if (RUNS_EMIT_PROBE == 1) return;                // timing probes only (tools/variants.sh): no output
   // match headers, and every run's segments into LDS (all loads of the pass in flight together)
   const int64_t mb = pre[c], eb = pre[W + c];
   if (M > 0) {                                     // (uniform) loads at clamped indices first, then the stores
@@ -435,7 +394,6 @@ __global__ __launch_bounds__(256) void runs_emit(const DevProgram* __restrict__ 
     }
   }
   __syncthreads();
-  if (RUNS_EMIT_PROBE == 2) return;
   // the entries, EMIT_T at a time: each run's index scattered at its first entry's offset in the window
   // (and the run going on from the previous window at offset 0), an inclusive max-scan over the window
   // gives every entry its run, then each thread writes entries tid, tid + 256, ... (coalesced stores, the
@@ -461,15 +419,9 @@ __global__ __launch_bounds__(256) void runs_emit(const DevProgram* __restrict__ 
                      v8.z & 0xFFFFu, v8.z >> 16, v8.w & 0xFFFFu, v8.w >> 16};
 #pragma unroll
     for (int q = 1; q < 8; q++) h[q] = h[q] > h[q - 1] ? h[q] : h[q - 1];
-    uint32_t m = h[7];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(m, d, 64);
-      if ((tid & 63) >= d) m = y > m ? y : m;
-    }
+    const uint32_t m = wave_scan_incl(h[7], tid & 63, ScanMax{});
     if ((tid & 63) == 63) s_w[tid >> 6] = int(m);
-    uint32_t ex = __shfl_up(m, 1, 64);
-    if ((tid & 63) == 0) ex = 0;
+    uint32_t ex = wave_prev(m, tid & 63, 0u);
     ex = ex > uint32_t(carry) ? ex : uint32_t(carry);
     __syncthreads();
     for (int w = 0; w < (tid >> 6); w++) ex = uint32_t(s_w[w]) > ex ? uint32_t(s_w[w]) : ex;

@@ -28,7 +28,8 @@
 #include <vector>
 
 #include "../../include/kcep.h"
-#include "launch.h"   // exclusive_scan (nfa.hip)
+#include "launch.h"   // exclusive_scan (scan.hip)
+#include "scan_dev.h"
 
 namespace kcep {
 int set_error(int code, const std::string& msg);   // abi.cpp: cep_last_error()
@@ -87,17 +88,7 @@ __global__ __launch_bounds__(PT_THREADS) void part_scatter(const int32_t* __rest
   __syncthreads();
   // per shard: exclusive scan of the thread counts in thread order
   for (int s = 0; s < G; s++) {
-    const int32_t v = cnt[s * PT_THREADS + t];
-    int32_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int32_t y = __shfl_up(x, d);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int32_t before = 0;
-    for (int i = 0; i < w; i++) before += wsum[i];
-    cnt[s * PT_THREADS + t] = before + x - v;
+    cnt[s * PT_THREADS + t] = block_scan_excl(cnt[s * PT_THREADS + t], wsum, lane, w);
     __syncthreads();
   }
   for (int j = 0; j < PT_PER; j++) {

@@ -1,5 +1,6 @@
 // stencil.hip -- scan, gather and post-processing of the stencil / chain path; the kernel itself is
 // in stencil_kernel.h, instantiated per K in stencil_k<N>.hip.
+#include "scan_dev.h"
 #include "stencil_kernel.h"
 
 namespace kcep {
@@ -9,23 +10,6 @@ template <int MAXK, class Fn>
 static inline hipError_t with_k(int k, Fn&& f) {
   if constexpr (MAXK == 0) return hipErrorInvalidValue;
   else return k == MAXK ? f(std::integral_constant<int, MAXK>{}) : with_k<MAXK - 1>(k, f);
-}
-
-// Exclusive prefix of x over the workgroup's threads (whole waves, at most 16), shuffle-up within the
-// wave and the wave sums through s_w (one barrier; the caller keeps s_w free until it)
-template <class T, class W>
-__device__ __forceinline__ T block_scan_excl(T x, W* s_w, int lane, int wid) {
-  T incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) s_w[wid] = incl;
-  __syncthreads();
-  T run = incl - x;
-  for (int w = 0; w < wid; w++) run += T(s_w[w]);
-  return run;
 }
 
 // Tiles' match slots -> one contiguous output in record order (the order

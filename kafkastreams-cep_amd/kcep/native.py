@@ -376,9 +376,10 @@ class Session:
 
     def key_profile(self):
         """``profile=True`` sessions: int64 array [n_keys, 25] (cep_key_profile): key, live-run max, run
-        evaluations, wall clock (100 MHz), 8 phase clocks, 3 scan counters, 0, workspace words, then the
-        words per allocation kind (first workspace, match output, heap, run queues, private lists,
-        aggregates, other) and the batch pool's share of them (kcep_dev.h NFA_PROFILE_W)."""
+        evaluations, wall clock (100 MHz), 11 phase clocks of the wave kernel's record loop (-1 each from
+        the lane kernel, which has none), the key's start, workspace words, then the words per allocation
+        kind (first workspace, match output, heap, run queues, private lists, aggregates, other) and the
+        batch pool's share of them (kcep_dev.h NFA_PROFILE_W)."""
         import numpy as np
         n = C.c_int64()
         check(lib().cep_key_profile(self.h, None, 0, C.byref(n)))
