@@ -134,6 +134,36 @@ typedef struct {
                                     (nfa_wave).  By default the wave kernel runs patterns whose keys' runs
                                     can multiply (a skip-till-next / skip-till-any stage) and the lane kernel
                                     the strict ones */
+#define CEP_SESSION_MASK_PASS 32  /* opt-in: the stencil / chain path also for strict patterns whose predicates
+                                    read several columns, compare columns, do arithmetic or read event
+                                    metadata.  A pattern is mask-pass eligible (cep_pattern_mask_pass) iff
+                                     - it has the stencil / chain shape: at most 8 stages, every stage strict,
+                                       no oneOrMore / times, no folds, distinct names, optionals not first and
+                                       at most 4 stages when any is optional;
+                                     - the direct lowering does not take it (cep_pattern_info.stencil_ok and
+                                       chain_ok are 0: a pattern the direct form takes keeps the direct form);
+                                     - every stage predicate (with its topic filter; for an optional stage also
+                                       its successor's predicate) reads nothing but the current record -- no
+                                       States.get / getOrElse, fold value or sequence condition -- and cannot
+                                       raise: an int or long `/` or `%` only by a constant other than 0
+                                       (double division is fine; `v != 0 && 10 / v > 1` is rejected);
+                                     - the predicates' bytecode fits the device limits.
+                                    On such a session a pre-pass kernel evaluates every predicate on every
+                                    record (the reference only where a run waits, which a predicate that cannot
+                                    raise does not show) and writes the record's stage mask as a column the
+                                    stencil / chain kernel reads.  With the flag the automatic path choice is
+                                    direct stencil / chain, then mask-pass stencil / chain, then runs, then
+                                    general; force_path = CEP_PATH_STENCIL / CEP_PATH_CHAIN opens for an
+                                    eligible pattern and fails as without the flag, the eligibility reason
+                                    appended, for any other.  Everything else is a stencil / chain session:
+                                    carry, CEP_BATCH_FILTER / ARRIVAL_ORDER / DELIVER, state export and import
+                                    (blobs move between mask-pass sessions of one pattern).  The pre-pass runs
+                                    compiled for the pattern unless CEP_SESSION_INTERPRET / KCEP_JIT=0
+                                    (cep_session_jit); cep_last_batch_ms covers it, cep_last_kernel_ms does
+                                    not.  Device-resident columns the predicates read must be 16-byte aligned.
+                                    The flag does nothing for a pattern the direct form takes or one that is
+                                    not eligible, so a host may set it unconditionally.  Without the flag every
+                                    pattern opens on the path it always did. */
 
 #define CEP_MEM_HOST 0
 #define CEP_MEM_DEVICE 1
@@ -270,6 +300,10 @@ int32_t cep_pattern_stage(const cep_pattern* p, int32_t sid, int32_t* name_id, i
  * a device path, else CEP_E_UNSUPPORTED with the reason in cep_last_error.  Host-only: the per-query
  * routing decision of a host (lowerable -> GPU, else the reference CEPProcessor) needs no device. */
 int cep_pattern_check(const cep_pattern* p, int32_t session_flags);
+/* CEP_OK if the pattern is mask-pass eligible (CEP_SESSION_MASK_PASS): *k = its stages, *chain = 1 if it
+ * runs as a chain (some stage optional); the outputs may be NULL.  Else CEP_E_UNSUPPORTED with the reason
+ * in cep_last_error (a pattern the direct stencil / chain form takes is not eligible).  Host-only. */
+int cep_pattern_mask_pass(const cep_pattern* p, int32_t* k, int32_t* chain);
 
 /* --- session: one per stream task (CEPProcessor.init :88-108) --- */
 int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** out);
@@ -313,8 +347,10 @@ int cep_batch_stopped(const cep_session* s, int64_t* keys, int64_t* records);
    session runs the built-in kernel)}; 25 int64 per key;
    out == NULL sets only *n_keys. */
 int cep_key_profile(cep_session* s, int64_t* out, int64_t cap, int64_t* n_keys);
-/* The HIP source of the pattern's compiled kernels for a path (CEP_PATH_RUNS), NUL-terminated;
-   with buf == NULL only *needed is set.  CEP_E_UNSUPPORTED if the path has none for this pattern. */
+/* The HIP source of the pattern's compiled kernels for a path (CEP_PATH_RUNS, CEP_PATH_GENERAL; for a
+   mask-pass eligible pattern CEP_PATH_STENCIL or CEP_PATH_CHAIN, either one: the pre-pass),
+   NUL-terminated; with buf == NULL only *needed is set.  CEP_E_UNSUPPORTED if the path has none for this
+   pattern. */
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed);
 /* Generate and compile (gfx950 code object, no device needed) the pattern's kernels for a path. */
 int cep_pattern_build_kernels(const cep_pattern* p, int path);

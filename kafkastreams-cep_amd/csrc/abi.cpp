@@ -145,16 +145,22 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   if (opts->mode != CEP_MODE_NFA && opts->mode != CEP_MODE_PROCESSOR) return fail(CEP_E_ARG, "bad mode");
   const Program& P = p->prog;
   int path = opts->force_path;
-  const int fast = P.stencil.chain ? CEP_PATH_CHAIN : CEP_PATH_STENCIL;   // the streaming kernel's flavour
-  if (path == 0) path = P.stencil_ok ? fast : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
+  // CEP_SESSION_MASK_PASS: where the direct lowering does not apply, the eligible pattern's mask-pass form
+  const bool mask_flag = (opts->flags & CEP_SESSION_MASK_PASS) && !P.stencil_ok;
+  const bool masked = mask_flag && P.mask_ok;
+  const StencilProgram* sp = P.stencil_ok ? &P.stencil : masked ? &P.mask_stencil : nullptr;
+  const int fast = sp && sp->chain ? CEP_PATH_CHAIN : CEP_PATH_STENCIL;   // the streaming kernel's flavour
+  if (path == 0) path = sp ? fast : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
   if (path == CEP_PATH_RUNS && !P.runs_ok) return fail(CEP_E_UNSUPPORTED, "runs path does not apply: " + P.runs_why);
-  if ((path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) && !P.stencil_ok)
-    return fail(CEP_E_UNSUPPORTED, "stencil path does not apply: " + P.stencil_why);
+  if ((path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) && !sp)
+    return fail(CEP_E_UNSUPPORTED, "stencil path does not apply: " + P.stencil_why +
+                                       (mask_flag ? "; mask pass does not apply: " + P.mask_why : std::string()));
   if (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) path = fast;
   if (path == CEP_PATH_GENERAL && !P.general_ok)
     return fail(CEP_E_UNSUPPORTED, "pattern cannot be lowered to the device NFA: " + P.general_why);
   if (path != CEP_PATH_STENCIL && path != CEP_PATH_CHAIN && path != CEP_PATH_GENERAL && path != CEP_PATH_RUNS)
     return fail(CEP_E_ARG, "bad path");
+  if (!P.stencil_ok && path != CEP_PATH_STENCIL && path != CEP_PATH_CHAIN) sp = nullptr;   // (a forced other path)
   const bool carry = opts->flags & CEP_SESSION_CARRY;
   if (carry && (opts->max_keys <= 0 || opts->max_keys > INT32_MAX))
     return fail(CEP_E_ARG, "carry sessions need max_keys (dense key ids in [0, max_keys))");
@@ -165,6 +171,8 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->pat = p;
   s->opts = *opts;
   s->path = path;
+  s->sp = sp ? sp : &P.stencil;                    // (never null: a collect before any push reads its k)
+  s->mask_pass = masked && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN);
   s->device = opts->device;
   auto cleanup = [&](int rc) {
     cep_session_close(s);
@@ -173,12 +181,12 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   const int64_t cap = std::max<int64_t>(opts->max_events, 1);
   if (cap >= (int64_t(1) << 31)) return cleanup(fail(CEP_E_ARG, "max_events must be < 2^31 per batch"));
   if (s->scal.ensure(64) || hipMemset(s->scal.p, 0, 64)) return cleanup(fail(CEP_E_HIP, "device allocation failed"));
-  if (P.stencil_ok && path != CEP_PATH_GENERAL) {
-    const int k = P.stencil.k;
+  if (sp && path != CEP_PATH_GENERAL) {
+    const int k = sp->k;
     const int64_t nt = stencil_tiles(cap);
     // a run ends at most once, so a batch has at most one match per start: its records, plus on chain
     // carry sessions the (at most K-1) starts in each batch key's halo
-    const int64_t out_cap = carry && P.stencil.chain ? cap + std::min<int64_t>(cap, opts->max_keys) * (k - 1) : cap;
+    const int64_t out_cap = carry && sp->chain ? cap + std::min<int64_t>(cap, opts->max_keys) * (k - 1) : cap;
     if (s->prog.ensure(sizeof(StencilProgram)) || s->status.ensure(sizeof(int64_t) * size_t(2 * nt + 2)) ||
         s->counter.ensure(sizeof(int64_t) * size_t(nt / 1024 + 4)) || s->total.ensure(64) || s->sum.ensure(64) ||
         s->out.ensure(sizeof(int32_t) * size_t(k) * size_t(out_cap)) ||
@@ -188,10 +196,15 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
                                            size_t(nt) * size_t(ST_SLOT_DENSE_ALLOC))))
       return cleanup(fail(CEP_E_HIP, "device allocation failed"));
     s->out_cap = out_cap;
-    if (hipMemcpy(s->prog.p, &P.stencil, sizeof(StencilProgram), hipMemcpyHostToDevice) ||
+    if (hipMemcpy(s->prog.p, sp, sizeof(StencilProgram), hipMemcpyHostToDevice) ||
         hipMemset(s->status.p, 0, s->status.cap) || hipMemset(s->counter.p, 0, s->counter.cap) ||
         hipMemset(s->total.p, 0, s->total.cap))
       return cleanup(fail(CEP_E_HIP, "device init failed"));
+  }
+  if (s->mask_pass) {
+    if (s->mprog.ensure(sizeof(MaskProgram)) || s->mcol.ensure(sizeof(int32_t) * size_t((cap + 3) & ~int64_t(3))) ||
+        hipMemcpy(s->mprog.p, &P.mask_prog, sizeof(MaskProgram), hipMemcpyHostToDevice))
+      return cleanup(fail(CEP_E_HIP, "device allocation failed"));
   }
   if (P.general_ok) {
     if (s->dprog.ensure(sizeof(DevProgram)) ||
@@ -201,7 +214,7 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   if (carry && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN)) {   // per key two halo slots, none written yet
     s->carry = true;
     if (s->halo.ensure(size_t(opts->max_keys) * sizeof(HaloHdr)) || s->hflags.ensure(16) ||
-        s->hpos.ensure(size_t(opts->max_keys) * 2 * size_t(std::max(1, P.stencil.k - 1)) * 8) ||
+        s->hpos.ensure(size_t(opts->max_keys) * 2 * size_t(std::max(1, sp->k - 1)) * 8) ||
         hipMemset(s->halo.p, 0, size_t(opts->max_keys) * sizeof(HaloHdr)) || hipMemset(s->hflags.p, 0, 16))
       return cleanup(fail(CEP_E_HIP, "device allocation failed"));
   } else if (carry && path == CEP_PATH_RUNS) {    // per key a carried tail, none yet (runs.hip)
@@ -236,6 +249,7 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   const char* env_jit = getenv("KCEP_JIT");
   s->jit_on = !(opts->flags & CEP_SESSION_INTERPRET) && !(env_jit && !strcmp(env_jit, "0"));
   if (s->jit_on && path == CEP_PATH_RUNS) s->jit = jit_runs(P, s->jit_why);   // on failure: built-in kernels
+  if (s->jit_on && s->mask_pass) s->jitm = jit_masks(P, s->jit_why);        // on failure: the built-in kernel
   if (s->jit_on && path == CEP_PATH_GENERAL) {
     s->jitg = jit_general(P, s->jit_why, s->opts.flags & CEP_SESSION_PROFILE);
     s->jitg_tried = true;
@@ -289,7 +303,7 @@ int cep_key_profile(cep_session* s, int64_t* out, int64_t cap, int64_t* n_keys) 
 
 int cep_session_jit(const cep_session* s) {
   if (!s) return 0;
-  return (s->path == CEP_PATH_RUNS && s->jit) || (s->path == CEP_PATH_GENERAL && s->jitg) ? 1 : 0;
+  return (s->path == CEP_PATH_RUNS && s->jit) || (s->path == CEP_PATH_GENERAL && s->jitg) || (s->mask_pass && s->jitm) ? 1 : 0;
 }
 
 int cep_session_wave(const cep_session* s) { return s && s->path == CEP_PATH_GENERAL && s->wave ? 1 : 0; }
@@ -304,12 +318,33 @@ int cep_batch_stopped(const cep_session* s, int64_t* keys, int64_t* records) {
 
 int cep_batch_attempts(const cep_session* s) { return s && s->last_path == CEP_PATH_GENERAL ? s->last_attempts : 0; }
 
+// the stencil / chain path has a compiled kernel only in its mask-pass form: the pre-pass
+static bool mask_pass_path(const Program& P, int path) {
+  return P.mask_ok && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN);   // (either names it, as at cep_session_open)
+}
+static int no_kernels(const Program& P, int path) {
+  if ((path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) && !P.mask_ok)
+    return fail(CEP_E_UNSUPPORTED, "no compiled kernels for this path: mask pass does not apply: " + P.mask_why);
+  return fail(CEP_E_UNSUPPORTED, "no compiled kernels for this path");
+}
+
+int cep_pattern_mask_pass(const cep_pattern* p, int32_t* k, int32_t* chain) {
+  if (!p) return fail(CEP_E_ARG, "null argument");
+  const Program& P = p->prog;
+  if (!P.mask_ok) return fail(CEP_E_UNSUPPORTED, "mask pass does not apply: " + P.mask_why);
+  if (k) *k = P.mask_stencil.k;
+  if (chain) *chain = P.mask_stencil.chain;
+  return CEP_OK;
+}
+
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed) {
   if (!p || !needed) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
-  if (!runs && !general) return fail(CEP_E_UNSUPPORTED, "no compiled kernels for this path");
+  const bool masks = mask_pass_path(p->prog, path);
+  if (!runs && !general && !masks) return no_kernels(p->prog, path);
   std::string why;
-  const std::string src = runs ? jit_source_runs(p->prog, why) : jit_source_general(p->prog, why);
+  const std::string src = masks ? jit_source_masks(p->prog, why)
+                                : runs ? jit_source_runs(p->prog, why) : jit_source_general(p->prog, why);
   if (src.empty()) return fail(CEP_E_UNSUPPORTED, "kernel generation failed: " + why);
   *needed = src.size() + 1;
   if (!buf) return CEP_OK;
@@ -321,9 +356,10 @@ int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t 
 int cep_pattern_build_kernels(const cep_pattern* p, int path) {
   if (!p) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
-  if (!runs && !general) return fail(CEP_E_UNSUPPORTED, "no compiled kernels for this path");
+  const bool masks = mask_pass_path(p->prog, path);
+  if (!runs && !general && !masks) return no_kernels(p->prog, path);
   std::string why;
-  if (!(runs ? jit_check_runs(p->prog, why) : jit_check_general(p->prog, why)))
+  if (!(masks ? jit_check_masks(p->prog, why) : runs ? jit_check_runs(p->prog, why) : jit_check_general(p->prog, why)))
     return fail(CEP_E_UNSUPPORTED, "kernel build failed: " + why);
   return CEP_OK;
 }
@@ -498,7 +534,7 @@ int cep_csr_check(const cep_matches* m, int64_t n_records, int32_t n_names) {
 // still in the device arrays)
 static int collect_delivered(cep_session* s, int slot, int64_t want, bool latest, cep_matches* o) {
   {
-    const StencilProgram& SP = s->pat->prog.stencil;
+    const StencilProgram& SP = *s->sp;
     const int k = SP.k;
     int64_t* hdr;
     int32_t* hkey;
@@ -611,7 +647,7 @@ int cep_collect(cep_session* s, cep_matches* o) {
     int rc = collect_delivered(s, int(s->dl_stamp & 1), s->dl_stamp, true, o);
     if (rc) return rc;
   } else {
-    const StencilProgram& SP = s->pat->prog.stencil;
+    const StencilProgram& SP = *s->sp;
     const int k = SP.k;
     int64_t nm = 0;
     if (s->pending && s->n > 0) HIPCHECK(hipMemcpyAsync(&nm, s->total.p, sizeof nm, hipMemcpyDeviceToHost, s->stream));
@@ -753,7 +789,7 @@ int cep_checksum(cep_session* s, uint64_t* sum, int64_t* n_matches) {
   HIPCHECK(hipStreamSynchronize(s->stream));
   nm = std::min(nm, s->out_cap);
   HIPCHECK(hipMemsetAsync(s->sum.p, 0, 8, s->stream));
-  const StencilProgram& SP = s->pat->prog.stencil;
+  const StencilProgram& SP = *s->sp;
   if (s->carry) {                                  // over stream positions
     if (s->opos.ensure(size_t(std::max<int64_t>(nm, 1)) * SP.k * 8)) return fail(CEP_E_HIP, "allocation failed");
     HIPCHECK(stencil_resolve_launch(s->d_key, s->out.as<int32_t>(), SP.k, nm, carry_args(s), s->opos.as<int64_t>(),

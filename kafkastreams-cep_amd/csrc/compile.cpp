@@ -433,11 +433,13 @@ bool build_table(StencilProgram& S) {
 // carries its own first Dewey digit and nodes are shared only at a stage both
 // runs consume, so the first-compatible traversal (MatchedEvent.java:90-99)
 // always returns the run's own predecessors.
-void analyse_stencil(Program& P) {
-  auto no = [&](const std::string& w) { P.stencil_ok = false; P.stencil_why = w; };
+// the shape the stencil / chain kernels take, whatever the predicates read: false + why; opt: bit i,
+// stage i is optional
+bool stencil_shape(const Program& P, uint32_t& opt, std::string& why) {
+  auto no = [&](const char* w) { why = w; return false; };
   const int k = int(P.pats.size());
   if (k > STENCIL_MAX_K) return no("more than 8 stages");
-  uint32_t opt = 0;
+  opt = 0;
   for (int i = 0; i < k; i++) {
     const auto& p = P.pats[i];
     if (p.strategy != S_STRICT) return no("non-strict selection strategy");
@@ -451,6 +453,17 @@ void analyse_stencil(Program& P) {
       if (P.pats[j].name_id == p.name_id) return no("duplicate stage names");
   }
   if (opt && k > CHAIN_MAX_K) return no("optional stages in a pattern of more than 4 stages");
+  return true;
+}
+
+void analyse_stencil(Program& P) {
+  auto no = [&](const std::string& w) { P.stencil_ok = false; P.stencil_why = w; };
+  const int k = int(P.pats.size());
+  uint32_t opt = 0;
+  {
+    std::string why;
+    if (!stencil_shape(P, opt, why)) return no(why);
+  }
   Lowering L;
   StencilProgram& S = P.stencil;
   memset(&S, 0, sizeof S);
@@ -714,6 +727,98 @@ bool event_only(const ExprP& e) {
   }
 }
 
+// why e can raise or reads more than the current record, or null: the pre-pass (masks.hip) evaluates
+// a slot on every record, the reference only where a run waits at the stage, so the difference is
+// invisible only for a slot that cannot throw.  Conservative: an integer / or % passes only with a
+// constant divisor other than 0 (`v != 0 && 10 / v > 1` is safe in Java and still rejected).
+const char* mask_unfit(const ExprP& e) {
+  if (!e) return nullptr;
+  switch (e->op) {
+    case OP_STATE_GET: case OP_STATE_GET_OR_ELSE: return "predicate reads an aggregate state (States.get)";
+    case OP_FOLD_CURR: return "predicate reads a fold's current value";
+    case OP_SEQ_AVG: case OP_SEQ_AGG: return "predicate is a sequence condition";
+    case OP_DIV: case OP_REM:
+      if (e->t != T_F64) {
+        const ExprP& d = e->b;
+        const bool nz = (d->op == OP_CONST_I32 && d->i32 != 0) || (d->op == OP_CONST_I64 && d->i64 != 0);
+        if (!nz) return "integer division or remainder whose divisor is not a constant other than 0 (it can raise)";
+      }
+      break;
+    default: break;
+  }
+  if (const char* w = mask_unfit(e->a)) return w;
+  return mask_unfit(e->b);
+}
+void mask_reads(const ExprP& e, MaskProgram& M) {
+  if (!e) return;
+  switch (e->op) {
+    case OP_FIELD: M.used |= 1 << e->col; break;
+    case OP_EV_KEY: M.meta |= MASK_META_KEY; break;
+    case OP_EV_TS: M.meta |= MASK_META_TS; break;
+    case OP_EV_OFFSET: M.meta |= MASK_META_OFFSET; break;
+    case OP_EV_PARTITION: M.meta |= MASK_META_PARTITION; break;
+    case OP_EV_TOPIC_EQ: M.meta |= MASK_META_TOPIC; break;
+    default: break;
+  }
+  mask_reads(e->a, M);
+  mask_reads(e->b, M);
+}
+
+// Mask-pass form of the stencil / chain path (kcep_internal.h Program::mask_ok): the shape of
+// analyse_stencil, predicates the direct lowering does not take, every slot event-only and total.
+void analyse_mask_pass(Program& P) {
+  auto no = [&](const std::string& w) { P.mask_ok = false; P.mask_why = w; };
+  uint32_t opt = 0;
+  {
+    std::string why;
+    if (!stencil_shape(P, opt, why)) return no(why);
+  }
+  if (P.stencil_ok) return no("the pattern lowers to the stencil path directly");
+  if (P.coltypes.size() > 16) return no("too many columns");
+  const int k = int(P.pats.size());
+  StencilProgram& S = P.mask_stencil;
+  MaskProgram& M = P.mask_prog;
+  memset(&S, 0, sizeof S);
+  memset(&M, 0, sizeof M);
+  CodeGen cg;
+  cg.names = &P.names;
+  const char* unfit = nullptr;
+  auto slot = [&](int s, const ExprP& pred) {
+    if (!unfit) unfit = mask_unfit(pred);
+    if (unfit || !event_only(pred)) return;
+    mask_reads(pred, M);
+    M.pslots |= 1 << s;
+    M.pc[s] = cg.emit(pred);
+  };
+  for (int i = 0; i < k; i++) {
+    const auto& p = P.pats[i];
+    S.name[i] = p.name_id;
+    slot(i, p.topic >= 0 ? mk(OP_AND, mk_topic(p.topic), p.pred) : p.pred);
+    // SKIP_PROCEED of an optional stage: successor predicate without its topic (StagesFactory.java:165)
+    if (opt >> i & 1) slot(CHAIN_MAX_K + i, P.pats[i + 1].pred);
+  }
+  if (unfit) return no(unfit);
+  if (!cg.ok) return no(cg.why);
+  if (cg.maxdepth > NFA_STACK) return no("expression nests deeper than the device operand stack");
+  if (cg.code.size() > size_t(NFA_MAX_CODE)) return no("predicate code too large");
+  M.ncols = int32_t(P.coltypes.size());
+  for (size_t c = 0; c < P.coltypes.size(); c++) M.coltype[c] = P.coltypes[c];
+  M.ncode = int32_t(cg.code.size());
+  memcpy(M.code, cg.code.data(), cg.code.size() * sizeof(int32_t));
+  // the stencil program over the mask column: an int32 value m in [0, 256) is its own stage mask
+  S.k = k;
+  S.chain = opt ? 1 : 0;
+  S.optmask = int32_t(opt);
+  S.pslots = M.pslots;
+  S.col = -1;
+  S.coltype = T_I32;
+  S.lut_lo = 0;
+  S.lut_n = 256;
+  for (int m = 0; m < 256; m++) S.lut[m] = uint8_t(m);
+  P.mask_ok = true;
+  P.mask_why.clear();
+}
+
 }  // namespace
 
 int lower_general(Program& P, std::string& why) {
@@ -856,6 +961,7 @@ int compile_ir(const uint8_t* ir, size_t len, Program& P, std::string& err) {
   analyse_stencil(P);
   P.general_ok = lower_general(P, P.general_why) == CEP_OK;
   analyse_runs(P);
+  analyse_mask_pass(P);
   P.has_seq = false;
   for (const auto& pd : P.pats) {
     P.has_seq = P.has_seq || uses_seq(pd.pred);

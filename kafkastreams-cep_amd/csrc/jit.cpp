@@ -92,8 +92,8 @@ std::string sv(int i) { return "s" + std::to_string(i); }
 // (state tag, Curr, division by zero) -- the ops after a failure compute discarded values and have no
 // side effects, so the result and the reported failure are the same; && / || jumps stay branches, so
 // what they skip never runs (Java's short circuit)
-bool gen_entry(const DevProgram& d, int pc0, std::string& o, std::string& why, bool branchfree) {
-  auto word = [&](int pc) { return pc >= 0 && pc < NFA_MAX_CODE ? d.code[pc] : 0; };
+bool gen_entry(const int32_t* code, int pc0, std::string& o, std::string& why, bool branchfree) {
+  auto word = [&](int pc) { return pc >= 0 && pc < NFA_MAX_CODE ? code[pc] : 0; };
   std::set<int> labels;
   bool has_seq = false;
   for (int pc = pc0;;) {                        // pass 1: jump targets
@@ -316,7 +316,7 @@ bool gen_program(const Program& P, std::string& o, std::string& why, bool branch
     gen_packed(o, "jst_slot_name", sn);
   }
   for (int pc : entries)
-    if (!gen_entry(d, pc, o, why, branchfree)) return false;
+    if (!gen_entry(d.code, pc, o, why, branchfree)) return false;
   o += "template <class Env>\n__device__ __forceinline__ bool jit_eval(int pc, Env& env, int64_t& r) {\n  switch (pc) {\n";
   for (int pc : entries) o += "    case " + std::to_string(pc) + ": return jf_" + std::to_string(pc) + "(env, r);\n";
   o += "  }\n  env.fail(CEP_E_BAD_IR);\n  return false;\n}\n";
@@ -461,6 +461,54 @@ std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why,
   static const char* const names[] = {"kcep_nfa_kernel", "kcep_nfa_wave", "kcep_nfa_order"};
   static hipFunction_t JitModule::* const slots[] = {&JitModule::nfa, &JitModule::nfa_wave, &JitModule::nfa_order};
   return build(src, names, slots, 3, why);
+}
+
+// The mask pre-pass (masks_dev.h): the MaskProgram's small fields as a constant (code[] stays zero: the
+// slots are compiled), one function per slot, and the kernel of masks.hip's shape around them.
+std::string jit_source_masks(const Program& P, std::string& why) {
+  if (!P.mask_ok) { why = "the pattern is not mask-pass eligible: " + P.mask_why; return ""; }
+  const MaskProgram& m = P.mask_prog;
+  std::string o = "#include \"interp.h\"\nnamespace kcep {\n";
+  o += "constexpr MaskProgram kcep_mask_prog = {" + std::to_string(m.pslots) + ",";
+  put_arr(o, m.pc, MASK_SLOTS);
+  o += "," + std::to_string(m.ncols) + "," + std::to_string(m.used) + "," + std::to_string(m.meta) + ",0,";
+  put_arr(o, m.coltype, 16);
+  o += "};\n";
+  std::set<int> entries;
+  for (int p = 0; p < MASK_SLOTS; p++)
+    if (m.pslots >> p & 1) entries.insert(m.pc[p]);
+  for (int pc : entries)
+    if (!gen_entry(m.code, pc, o, why, true)) return "";
+  o += "template <class Env>\n__device__ __forceinline__ bool jit_eval(int pc, Env& env, int64_t& r) {\n  switch (pc) {\n";
+  for (int pc : entries) o += "    case " + std::to_string(pc) + ": return jf_" + std::to_string(pc) + "(env, r);\n";
+  o += "  }\n  return false;\n}\n";
+  o += R"(struct MaskJitTab {
+  static constexpr int NC = 16;                   // every column read is held in registers (constant indices)
+  __device__ __forceinline__ const MaskProgram& prog() const { return kcep_mask_prog; }
+  template <class Env>
+  __device__ __forceinline__ bool eval(int pc, Env& env, int64_t& v) const { return jit_eval(pc, env, v); }
+};
+}  // namespace kcep
+#include "masks_dev.h"
+extern "C" __global__ __launch_bounds__(kcep::MK_THREADS) void kcep_masks(kcep::MaskArgs A) {
+  kcep::masks_body(kcep::MaskJitTab{}, A);
+}
+)";
+  return o;
+}
+
+std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why) {
+  const std::string src = jit_source_masks(P, why);
+  if (src.empty()) return nullptr;
+  static const char* const names[] = {"kcep_masks"};
+  static hipFunction_t JitModule::* const slots[] = {&JitModule::masks};
+  return build(src, names, slots, 1, why);
+}
+
+bool jit_check_masks(const Program& P, std::string& why) {
+  const std::string src = jit_source_masks(P, why);
+  std::vector<char> code;
+  return !src.empty() && compile(src, code, why);
 }
 
 bool jit_check_general(const Program& P, std::string& why) {

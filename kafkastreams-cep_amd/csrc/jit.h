@@ -18,6 +18,7 @@ struct JitModule {
   hipFunction_t nfa = nullptr;          // nfa_dev.h nfa_kernel_body (general path)
   hipFunction_t nfa_wave = nullptr;     // nfa_wave.h nfa_wave_body, one key per wave (general path)
   hipFunction_t nfa_order = nullptr;    // nfa_dev.h nfa_order_bits_body, the wave kernel's schedule estimate
+  hipFunction_t masks = nullptr;        // masks_dev.h masks_body<MaskJitTab>, the mask pre-pass
   ~JitModule();
 };
 
@@ -38,5 +39,10 @@ std::string jit_source_general(const Program& P, std::string& why, bool phases =
 // CEP_BATCH_STOP_AT_ERROR build, a module of its own that only flagged batches compile and launch
 std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases = false, bool stop = false);
 bool jit_check_general(const Program& P, std::string& why);
+
+// the same for the mask pre-pass of a mask-pass eligible pattern (masks_dev.h)
+std::string jit_source_masks(const Program& P, std::string& why);
+std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why);
+bool jit_check_masks(const Program& P, std::string& why);
 
 }  // namespace kcep

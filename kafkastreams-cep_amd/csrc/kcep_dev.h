@@ -212,6 +212,37 @@ struct RunsArgs {
   int32_t chunk;                  // items per wave (a power of two <= RUNS_CHUNK; runs_chunk)
   unsigned long long* max_span;   // runs_sim: the longest completed run's span (end - start), atomicMax
 };
+// ---- mask pre-pass (masks.hip, CEP_SESSION_MASK_PASS) ----
+// The predicate slots of a strict pattern (kcep_internal.h StencilProgram: slot i = stage i's predicate
+// and topic filter, slot 4 + i = the successor's predicate of optional stage i) as bytecode, each a pure
+// and total function of one record: the pre-pass evaluates them on every record and writes the record's
+// stage-mask byte as an int32 column, which the stencil / chain kernels then read as their value column.
+constexpr int MASK_SLOTS = 8;
+enum : int32_t { MASK_META_TS = 1, MASK_META_OFFSET = 2, MASK_META_PARTITION = 4, MASK_META_TOPIC = 8, MASK_META_KEY = 16 };
+struct MaskProgram {
+  int32_t pslots;                 // bit p: slot p is in use
+  int32_t pc[MASK_SLOTS];         // its code offset
+  int32_t ncols;
+  int32_t used;                   // bit c: some slot reads value column c
+  int32_t meta;                   // MASK_META_*: the event metadata some slot reads
+  int32_t ncode;
+  int32_t coltype[16];
+  int32_t code[NFA_MAX_CODE];
+};
+struct MaskArgs {
+  const MaskProgram* P;
+  const int32_t* key;
+  const int32_t* topic;           // null: every record on topic 0
+  const int32_t* partition;       // null: 0
+  const int64_t* offset;          // null: the stream position
+  const int64_t* ts;              // null: the stream position
+  const int64_t* pos;             // stream position of each record; null: base + record index
+  const void* cols[16];
+  int64_t n;
+  int64_t base;
+  int32_t* mask;                  // out: n stage masks (allocated for n rounded up to 4)
+};
+
 constexpr int RUNS_MAX_SEGS = 8;
 constexpr int RUNS_CHUNK = 1024;
 KCEP_HD inline int32_t runs_chunk(int64_t items) {

@@ -119,6 +119,14 @@ struct Program {
   bool has_seq = false;              // some predicate or fold is a SequenceMatcher (OP_SEQ_*)
   std::string runs_why;
   StencilProgram stencil{};
+  // mask-pass form (compile.cpp analyse_mask_pass; CEP_SESSION_MASK_PASS sessions): the structural
+  // conditions of the stencil / chain path hold but the predicates do not lower to intervals of one
+  // column, and every predicate slot is an event-only, total expression -- the slots as bytecode for the
+  // pre-pass (masks.hip), and the stencil program that reads the mask column it writes
+  bool mask_ok = false;
+  std::string mask_why;
+  StencilProgram mask_stencil{};
+  MaskProgram mask_prog{};
 };
 
 // ---- carried state of the stencil / chain paths (CEP_SESSION_CARRY) ----

@@ -189,6 +189,9 @@ hipError_t stencil_resolve_launch(const int32_t* key, const int32_t* out, int k,
 hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k, const int64_t* total, int64_t out_cap,
                                   const StencilCarry& C, const DeliverArgs& D, hipStream_t st);
 
+// ---- masks.hip: the mask pre-pass of CEP_SESSION_MASK_PASS sessions (jf: the per-pattern kernel, or null) ----
+hipError_t masks_launch(const MaskArgs& A, hipStream_t st, hipFunction_t jf);
+
 // ---- scan.hip: the device utilities every path shares ----
 hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, int64_t* tmp, hipStream_t st);
 hipError_t exclusive_scan_pair(const int64_t* in0, const int64_t* in1, int64_t n, const int64_t* n_dev, int64_t* out0,

@@ -96,13 +96,53 @@ void dl_layout(const cep_session* s, int slot, int64_t*& hdr, int32_t*& hkey, in
   hpos = hdr + 4 + (s->dl_cap + 1) / 2 + 1;
 }
 
+static int stage_inputs(cep_session* s, const cep_batch* b, hipStream_t st, NfaArgs& A, bool zero_copy);
+
+// A mask-pass session's batch (CEP_SESSION_MASK_PASS): every column on the device, then the pre-pass
+// (masks.hip) over the columns the path is about to read -- the caller's, group_batch's or filter_batch's,
+// with their stream positions -- writes the mask column the stencil / chain kernel takes as its value column
+static int push_masks(cep_session* s, const cep_batch* b, hipStream_t st, const int32_t*& key, const void*& col) {
+  const MaskProgram& MP = s->pat->prog.mask_prog;
+  NfaArgs in{};
+  int rc = stage_inputs(s, b, st, in, true);
+  if (rc) return rc;
+  MaskArgs M{};
+  M.P = s->mprog.as<MaskProgram>();
+  M.key = in.key;
+  M.topic = (MP.meta & MASK_META_TOPIC) ? in.topic : nullptr;
+  M.partition = (MP.meta & MASK_META_PARTITION) ? in.partition : nullptr;
+  M.offset = (MP.meta & MASK_META_OFFSET) ? in.offset : nullptr;
+  M.ts = (MP.meta & MASK_META_TS) ? in.ts : nullptr;
+  M.pos = s->cur_pos;
+  M.n = b->n;
+  M.base = s->carry ? s->base : 0;
+  M.mask = s->mcol.as<int32_t>();
+  uintptr_t bits = reinterpret_cast<uintptr_t>(M.key) | reinterpret_cast<uintptr_t>(M.topic) |
+                   reinterpret_cast<uintptr_t>(M.partition) | reinterpret_cast<uintptr_t>(M.offset) |
+                   reinterpret_cast<uintptr_t>(M.ts) | reinterpret_cast<uintptr_t>(M.pos);
+  for (int c = 0; c < b->n_cols && c < 16; c++)
+    if (MP.used >> c & 1) {
+      M.cols[c] = in.cols[c];
+      bits |= reinterpret_cast<uintptr_t>(M.cols[c]);
+    }
+  if (bits & 15) return fail(CEP_E_ARG, "device columns must be 16-byte aligned");
+  if (size_t(b->n) * 4 > s->mcol.cap) return fail(CEP_E_ARG, "batch larger than the session capacity");
+  HIPCHECK(masks_launch(M, st, s->jitm ? s->jitm->masks : nullptr));
+  key = in.key;
+  col = M.mask;
+  return CEP_OK;
+}
+
 int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st) {
-  const StencilProgram& SP = s->pat->prog.stencil;
-  const void* col = b->n_cols ? b->cols[SP.col] : nullptr;
+  const StencilProgram& SP = *s->sp;
+  const void* col = b->n_cols && !s->mask_pass ? b->cols[SP.col] : nullptr;
   const int32_t* key = b->key_id;
   const int32_t* topic = SP.use_topic ? b->topic : nullptr;
   const size_t vs = type_size(SP.coltype);
-  if (b->mem == CEP_MEM_HOST && b->n > 0) {
+  if (s->mask_pass) {
+    int rc = push_masks(s, b, st, key, col);
+    if (rc) return rc;
+  } else if (b->mem == CEP_MEM_HOST && b->n > 0) {
     HostArr arrs[3] = {{key, size_t(b->n) * 4, reinterpret_cast<const void**>(&key)},
                        {col, size_t(b->n) * vs, &col},
                        {topic, size_t(b->n) * 4, reinterpret_cast<const void**>(&topic)}};

@@ -105,6 +105,10 @@ struct cep_session {
   const cep_pattern* pat = nullptr;
   cep_opts opts{};
   int path = 0;                 // preferred path
+  // the stencil program the session's stencil / chain batches run: the pattern's direct
+  // lowering, or on a CEP_SESSION_MASK_PASS session of an eligible pattern its mask-pass form
+  const kcep::StencilProgram* sp = nullptr;
+  bool mask_pass = false;       // stencil / chain batches run the pre-pass (masks.hip) first
   int last_path = 0;            // path of the last batch
   int device = 0;
   hipStream_t stream = nullptr;
@@ -116,6 +120,7 @@ struct cep_session {
   DBuf prog, out, status, counter, total, sum, mkey, slots;   // status: tile counts + prefixes; counter: scan scratch
   int64_t out_cap = 0;
   const int32_t* d_key = nullptr;
+  DBuf mprog, mcol;             // mask pass: the MaskProgram; the mask column (max_events rounded up to 4 int32)
   // ---- staging of host-resident batches (stage_host): a pinned ring the caller's columns are copied
   // into in chunks, each chunk moved by one async copy into one packed device image; caller memory
   // that is itself pinned is copied from directly and the push waits for that copy ----
@@ -170,6 +175,7 @@ struct cep_session {
   // kernels compiled for the pattern (jit.cpp); null: the built-in interpreting kernels run
   bool jit_on = false;                     // allowed (not CEP_SESSION_INTERPRET / KCEP_JIT=0)
   std::shared_ptr<const JitModule> jit;    // runs path
+  std::shared_ptr<const JitModule> jitm;   // mask pass: the pre-pass kernel
   std::shared_ptr<const JitModule> jitg;   // general path (built at open, or at the first general batch)
   bool jitg_tried = false;
   std::shared_ptr<const JitModule> jitg_stop;   // its CEP_BATCH_STOP_AT_ERROR build (at the first flagged batch)
@@ -232,7 +238,7 @@ inline int32_t max_keys32(const cep_session* s) { return int32_t(std::min<int64_
 
 // the halo arguments of the last stencil batch (its stamp and stream position)
 inline StencilCarry carry_args(const cep_session* s) {
-  return StencilCarry{s->halo.as<HaloHdr>(), s->hpos.as<int64_t>(), s->pat->prog.stencil.k - 1, s->halo_stamp,
+  return StencilCarry{s->halo.as<HaloHdr>(), s->hpos.as<int64_t>(), s->sp->k - 1, s->halo_stamp,
                       max_keys32(s), s->halo_base,
                       s->hflags.as<unsigned long long>() + (s->halo_stamp & 1), s->last_gpos};
 }

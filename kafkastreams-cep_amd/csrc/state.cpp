@@ -104,7 +104,7 @@ constexpr uint32_t kHaloMagic = 0x4853434Bu;   // "KCSH"
 int halo_newest(const HaloHdr& h) { return h.stamp[1] > h.stamp[0] ? 1 : 0; }
 
 int halo_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_t cap, size_t* needed) {
-  const int km1 = s->pat->prog.stencil.k - 1;
+  const int km1 = s->sp->k - 1;
   const size_t nk = size_t(std::max(0, key_hi - key_lo));
   std::vector<HaloHdr> tab(nk);
   std::vector<int64_t> pos(nk * 2 * size_t(km1));
@@ -147,7 +147,7 @@ int halo_import(cep_session* s, const uint8_t* p, size_t len, uint32_t ver) {
   int64_t base;
   int32_t nkeys;
   memcpy(&base, p + 8, 8); memcpy(&nkeys, p + 16, 4);
-  const int K = s->pat->prog.stencil.k;
+  const int K = s->sp->k;
   struct Row { int32_t k, cnt; uint64_t masks; int64_t pos[STENCIL_MAX_K - 1]; };
   std::vector<Row> rows;
   size_t at = 20;
@@ -446,7 +446,7 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
     marks_dirty = true;
   };
   if (halo_session(s)) {
-    const int km1 = s->pat->prog.stencil.k - 1;
+    const int km1 = s->sp->k - 1;
     const int64_t nk = s->opts.max_keys;
     std::vector<HaloHdr> tab(static_cast<size_t>(nk));
     std::vector<int64_t> pos(static_cast<size_t>(nk) * 2 * size_t(km1));

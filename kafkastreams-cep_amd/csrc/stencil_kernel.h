@@ -198,7 +198,14 @@ __device__ __forceinline__ void masks_of_chunk(const Chunk<VT, TOPIC>& c, const 
 
 template <class VT, bool TOPIC>
 __device__ __forceinline__ uint32_t mask_of(const StencilProgram* __restrict__ P, const uint8_t* s_tab,
-                                            const uint8_t* s_nan, VT v, int32_t t) {
+                                            const uint8_t* s_nan, VT v, int32_t t, const uint8_t* s_lut) {
+  if constexpr (!TOPIC && !std::is_same<VT, double>::value) {
+    const int32_t lut_n = P->lut_n;
+    if (lut_n > 0) {                               // dense table, as masks_of_chunk (uniform branch)
+      const int64_t dv = int64_t(v) - P->lut_lo;
+      return dv < 0 ? s_tab[0] : dv >= lut_n ? s_tab[P->nbp] : s_lut[dv];
+    }
+  }
   int iv = 0, it = 0;
   for (int b = 0; b < P->nbp; b++) iv += bp_at<VT>(P, b) <= v ? 1 : 0;
   if constexpr (TOPIC)
@@ -537,7 +544,7 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
         *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
       }
       if (tid < 16) {                             // halo: the records before the tile (r' = 0..15)
-        if (j == 0 && h_first) h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top);
+        if (j == 0 && h_first) h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top, s_lut);
         if constexpr (!CARRY) s_key[kpos(tid)] = halo_lane ? h_key : INT32_MIN;
         s_mask[tid] = halo_lane ? uint8_t(h_mask) : 0;
       }
@@ -932,7 +939,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   __syncthreads();                                // the tables
   uint32_t h_mask = 0;
   if (halo_lane && hg >= 0)
-    h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top) | (uint32_t(CARRY && hg > 0 && h_prev == h_key) << 7);
+    h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top, s_lut) | (uint32_t(CARRY && hg > 0 && h_prev == h_key) << 7);
   int32_t h_bk = h_key;                           // carry: the history records' keys
   bool twice = false;                             // carry: a key claimed twice in this batch
 

@@ -36,6 +36,7 @@ SESSION_INTERPRET = 2
 SESSION_PROFILE = 4
 SESSION_LANE_NFA = 8
 SESSION_WAVE_NFA = 16
+SESSION_MASK_PASS = 32     # opt-in: stencil / chain path for eligible multi-column predicates (CompiledPattern.mask_pass)
 
 
 class CepError(RuntimeError):
@@ -82,7 +83,7 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_match_count_to", "cep_state_evict", "cep_state_import_keys", "cep_state_positions",
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
            "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped",
-           "cep_filter_tile_records"]
+           "cep_filter_tile_records", "cep_pattern_mask_pass"]
 
 _lib = None
 
@@ -145,6 +146,8 @@ def lib():
     if hasattr(L, "cep_filter_tile_records"):   # (KCEP_LIB A/B runs may load an older build)
         L.cep_filter_tile_records.argtypes = []
         L.cep_filter_tile_records.restype = C.c_int32
+    if hasattr(L, "cep_pattern_mask_pass"):     # (KCEP_LIB A/B runs may load an older build)
+        L.cep_pattern_mask_pass.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -223,6 +226,17 @@ class CompiledPattern:
         check(L.cep_state_to_reference(self.h, blob, len(blob), buf, n.value, C.byref(n)))
         return buf.raw[:n.value]
 
+    @property
+    def mask_pass(self):
+        """cep_pattern_mask_pass: ``(ok, k, chain, why)`` -- whether a ``mask_pass=True`` session runs the
+        pattern on the stencil / chain path through the mask pre-pass, its stage count, whether it runs as a
+        chain, and the reason when it does not (a pattern the direct stencil form takes is not eligible)."""
+        k, chain = C.c_int32(), C.c_int32()
+        rc = lib().cep_pattern_mask_pass(self.h, C.byref(k), C.byref(chain))
+        if rc == CEP_OK:
+            return True, k.value, bool(chain.value), ""
+        return False, 0, False, lib().cep_last_error().decode()
+
     def kernel_source(self, path=PATH_RUNS) -> str:
         """HIP source of the kernels compiled for this pattern (cep_pattern_kernel_source)."""
         n = C.c_size_t()
@@ -252,20 +266,23 @@ class Session:
 
     def __init__(self, pattern: CompiledPattern, max_events: int, mode=MODE_PROCESSOR, device=0, force_path=0,
                  carry=False, max_keys=0, interpret=False, profile=False, max_key_words=0, lane_nfa=None,
-                 max_pool_bytes=0):
+                 max_pool_bytes=0, mask_pass=False):
         """``carry=True``: every key's NFA state continues across batches (CEP_SESSION_CARRY);
         key ids must then be dense in [0, max_keys) and record positions are stream positions.
         ``interpret=True``: the built-in interpreting kernels instead of kernels compiled for the
         pattern (CEP_SESSION_INTERPRET); ``self.jit`` says which run.  ``max_key_words``: the
         general path's per-key workspace cap -- a key over it is handed back per key
         (``batch_errors`` lists it with RunCapacity), every other key completes.  ``max_pool_bytes``:
-        how far the general path's workspace pool may grow for a batch (0: a quarter of the HBM)."""
+        how far the general path's workspace pool may grow for a batch (0: a quarter of the HBM).
+        ``mask_pass=True`` (CEP_SESSION_MASK_PASS): a strict pattern whose predicates read several
+        columns, arithmetic or event metadata (``CompiledPattern.mask_pass``) opens on the stencil / chain
+        path, a pre-pass kernel writing each record's stage mask; no effect on any other pattern."""
         self.pattern = pattern
         self.h = C.c_void_p()
         # lane_nfa: None = the library's choice, True = one key per lane, False = one key per wave
         flags = ((SESSION_CARRY if carry else 0) | (SESSION_INTERPRET if interpret else 0) |
                  (SESSION_PROFILE if profile else 0) | (SESSION_LANE_NFA if lane_nfa else 0) |
-                 (SESSION_WAVE_NFA if lane_nfa is False else 0))
+                 (SESSION_WAVE_NFA if lane_nfa is False else 0) | (SESSION_MASK_PASS if mask_pass else 0))
         o = Opts(device, mode, force_path, flags, max_events, max_keys, 0.0, max_key_words, max_pool_bytes)
         check(lib().cep_session_open(pattern.h, C.byref(o), C.byref(self.h)))
         self.path = lib().cep_session_path(self.h)

@@ -109,7 +109,7 @@ class GpuCEPProcessor:
     def __init__(self, queryName: str, pattern: Union[Pattern, bytes], schema: Schema, decoder: ColumnDecoder,
                  batch_size: int = 1 << 16, max_keys: int = 1 << 20, device: int = 0,
                  mode: int = N.MODE_PROCESSOR, prune_at: int = 1 << 20, max_key_words: int = 0,
-                 stop_at_error: bool = False, device_filter: bool = False):
+                 stop_at_error: bool = False, device_filter: bool = False, mask_pass: bool = False):
         if decoder.schema is not schema and decoder.schema.columns != schema.columns:
             raise ValueError("decoder and pattern use different schemas")
         self.queryName = queryName.lower().replace("\\s+", "")
@@ -126,6 +126,9 @@ class GpuCEPProcessor:
         # of flush()'s per-record loop; the marks are then part of the session's state blobs and
         # checkpoints carry no "hwm" entry
         self.device_filter = bool(device_filter)
+        # CEP_SESSION_MASK_PASS for the session init() opens: an eligible multi-column strict pattern then
+        # runs on the stencil / chain path (native.CompiledPattern.mask_pass); no effect on other patterns
+        self.mask_pass = bool(mask_pass)
         self.device = device
         self.mode = mode
         ir = pattern if isinstance(pattern, (bytes, bytearray)) else pattern.to_ir(schema)
@@ -159,7 +162,8 @@ class GpuCEPProcessor:
         check the host logic without a GPU)."""
         self._forward = forward
         self.session = session or N.Session(self.compiled, self.batch_size, mode=self.mode, device=self.device,
-                                            carry=True, max_keys=self.max_keys, max_key_words=self.max_key_words)
+                                            carry=True, max_keys=self.max_keys, max_key_words=self.max_key_words,
+                                            mask_pass=self.mask_pass)
 
     def process(self, key, value, topic: str, partition: int, offset: int, timestamp: int):
         """One record with its ``ProcessorContext`` metadata."""
