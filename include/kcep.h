@@ -61,6 +61,9 @@ extern "C" {
                                      oneOrMore with exclusive TAKE/PROCEED): one lane per start record */
 #define CEP_PATH_CHAIN 3          /* strict single-cardinality patterns with optional() stages: the stencil
                                      kernel with deterministic per-start runs (variable-length matches) */
+#define CEP_PATH_FOLLOW 5         /* strict and skip-till-next (followedBy) stages of cardinality ONE / times(n):
+                                     one deterministic walk per start record over per-slot bitmaps
+                                     (CEP_SESSION_FOLLOW, cep_pattern_follow); sessions without carry */
 
 typedef struct cep_pattern cep_pattern;
 typedef struct cep_session cep_session;
@@ -163,6 +166,41 @@ typedef struct {
                                     not.  Device-resident columns the predicates read must be 16-byte aligned.
                                     The flag does nothing for a pattern the direct form takes or one that is
                                     not eligible, so a host may set it unconditionally.  Without the flag every
+                                    pattern opens on the path it always did. */
+
+#define CEP_SESSION_FOLLOW 64     /* opt-in: the follow path (CEP_PATH_FOLLOW) for patterns with skip-till-next
+                                    stages, which otherwise run on the general NFA.  A pattern is follow
+                                    eligible (cep_pattern_follow) iff
+                                     - every stage has cardinality ONE or times(n): no oneOrMore, zeroOrMore or
+                                       optional; no folds; distinct stage names;
+                                     - the first stage is strict and has no times; every other stage is strict
+                                       or skip-till-next (no skip-till-any), and at least one is skip-till-next
+                                       (an all-strict pattern keeps its stencil, chain or runs path);
+                                     - its slots, a times(n) stage counting n, are at most 8;
+                                     - every predicate, with its topic filter, lowers as on the direct stencil
+                                       path: comparisons of one column with constants, at most 16 intervals.
+                                    A skip-till-next stage ignores exactly the records its predicate rejects, so
+                                    no run of such a pattern branches: a record satisfying the first stage
+                                    starts one walk -- a strict slot takes the key's next record or the walk
+                                    dies, a skip-till-next slot takes the key's next record satisfying it -- and
+                                    a walk that completes inside the batch is one match, emitted at its last
+                                    record; matches of one record come out by ascending start.  The output
+                                    equals the general path's in both CEP_MODE_*, without its run queues,
+                                    Dewey versions and shared buffer.  With the flag the automatic path choice
+                                    is direct stencil / chain, mask-pass stencil / chain, follow, runs, general;
+                                    force_path = CEP_PATH_FOLLOW opens an eligible pattern with or without the
+                                    flag and fails with CEP_E_UNSUPPORTED and the eligibility reason for any
+                                    other.  Sessions without CEP_SESSION_CARRY only: with CEP_SESSION_CARRY the
+                                    flag does nothing (the session opens where it always did) and force_path =
+                                    CEP_PATH_FOLLOW fails with CEP_E_UNSUPPORTED.  A batch with null records
+                                    (valid), or in CEP_MODE_PROCESSOR with offsets not declared
+                                    CEP_BATCH_OFFSETS_MONOTONE, runs on the general path (cep_matches.path says
+                                    so), as on a stencil session without carry; CEP_BATCH_STOP_AT_ERROR on a
+                                    follow batch fails with CEP_E_UNSUPPORTED.  Device-resident key, value and
+                                    topic columns must be 16-byte aligned.  cep_last_kernel_ms times the
+                                    streaming bitmap kernel, cep_last_batch_ms the whole push, which waits once
+                                    for the match count.  The flag does nothing for a pattern that is not
+                                    eligible, so a host may set it unconditionally.  Without the flag every
                                     pattern opens on the path it always did. */
 
 #define CEP_MEM_HOST 0
@@ -304,6 +342,10 @@ int cep_pattern_check(const cep_pattern* p, int32_t session_flags);
  * runs as a chain (some stage optional); the outputs may be NULL.  Else CEP_E_UNSUPPORTED with the reason
  * in cep_last_error (a pattern the direct stencil / chain form takes is not eligible).  Host-only. */
 int cep_pattern_mask_pass(const cep_pattern* p, int32_t* k, int32_t* chain);
+/* CEP_OK if the pattern is follow eligible (CEP_SESSION_FOLLOW, CEP_PATH_FOLLOW): *k = its slots (a times(n)
+ * stage counts n), bit s of *next_mask = slot s is skip-till-next; the outputs may be NULL.  Else
+ * CEP_E_UNSUPPORTED with the reason in cep_last_error.  Host-only, as cep_pattern_mask_pass. */
+int cep_pattern_follow(const cep_pattern* p, int32_t* k, uint32_t* next_mask);
 
 /* --- session: one per stream task (CEPProcessor.init :88-108) --- */
 int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** out);
@@ -388,6 +430,9 @@ int cep_csr_check(const cep_matches* m, int64_t n_records, int32_t n_names);
 int64_t cep_batch_id(const cep_session* s);
 /* CEP_BATCH_FILTER: records per workgroup of the admission scan (a key's segment may cross any number of them) */
 int32_t cep_filter_tile_records(void);
+/* CEP_PATH_FOLLOW: records per workgroup of the streaming bitmap kernel (a key's segment and a walk may cross
+ * any number of them) */
+int32_t cep_follow_tile_records(void);
 int cep_batch_ready(cep_session* s, int64_t id);
 int cep_collect_batch(cep_session* s, int64_t id, cep_matches* out);
 

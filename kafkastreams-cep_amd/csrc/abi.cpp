@@ -12,6 +12,7 @@
 // Device paths:
 //   stencil  (stencil.hip)  strict single-cardinality patterns, SURVEY Q9
 //   runs     (runs.hip)     deterministic strict runs
+//   follow   (follow.hip)   strict and skip-till-next stages: one deterministic walk per start (opt-in)
 //   general  (nfa.hip)      every pattern the IR expresses: one lane (or wave) per key
 //                           running the reference NFA over an HBM arena
 #include <dlfcn.h>
@@ -150,7 +151,14 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   const bool masked = mask_flag && P.mask_ok;
   const StencilProgram* sp = P.stencil_ok ? &P.stencil : masked ? &P.mask_stencil : nullptr;
   const int fast = sp && sp->chain ? CEP_PATH_CHAIN : CEP_PATH_STENCIL;   // the streaming kernel's flavour
-  if (path == 0) path = sp ? fast : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
+  const bool carry = opts->flags & CEP_SESSION_CARRY;
+  // CEP_SESSION_FOLLOW: an eligible pattern's skip-till-next walks, on sessions without carry
+  const bool follow_flag = (opts->flags & CEP_SESSION_FOLLOW) && !carry && P.follow_ok;
+  if (path == 0) path = sp ? fast : follow_flag ? CEP_PATH_FOLLOW : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
+  if (path == CEP_PATH_FOLLOW && !P.follow_ok)
+    return fail(CEP_E_UNSUPPORTED, "follow path does not apply: " + P.follow_why);
+  if (path == CEP_PATH_FOLLOW && carry)
+    return fail(CEP_E_UNSUPPORTED, "follow path does not apply: it takes sessions without CEP_SESSION_CARRY");
   if (path == CEP_PATH_RUNS && !P.runs_ok) return fail(CEP_E_UNSUPPORTED, "runs path does not apply: " + P.runs_why);
   if ((path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) && !sp)
     return fail(CEP_E_UNSUPPORTED, "stencil path does not apply: " + P.stencil_why +
@@ -158,10 +166,11 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   if (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) path = fast;
   if (path == CEP_PATH_GENERAL && !P.general_ok)
     return fail(CEP_E_UNSUPPORTED, "pattern cannot be lowered to the device NFA: " + P.general_why);
-  if (path != CEP_PATH_STENCIL && path != CEP_PATH_CHAIN && path != CEP_PATH_GENERAL && path != CEP_PATH_RUNS)
+  if (path != CEP_PATH_STENCIL && path != CEP_PATH_CHAIN && path != CEP_PATH_GENERAL && path != CEP_PATH_RUNS &&
+      path != CEP_PATH_FOLLOW)
     return fail(CEP_E_ARG, "bad path");
   if (!P.stencil_ok && path != CEP_PATH_STENCIL && path != CEP_PATH_CHAIN) sp = nullptr;   // (a forced other path)
-  const bool carry = opts->flags & CEP_SESSION_CARRY;
+  const bool follow = path == CEP_PATH_FOLLOW;
   if (carry && (opts->max_keys <= 0 || opts->max_keys > INT32_MAX))
     return fail(CEP_E_ARG, "carry sessions need max_keys (dense key ids in [0, max_keys))");
   if (carry && !P.general_ok)
@@ -171,7 +180,7 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->pat = p;
   s->opts = *opts;
   s->path = path;
-  s->sp = sp ? sp : &P.stencil;                    // (never null: a collect before any push reads its k)
+  s->sp = follow ? &P.follow : sp ? sp : &P.stencil;   // (never null: a collect before any push reads its k)
   s->mask_pass = masked && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN);
   s->device = opts->device;
   auto cleanup = [&](int rc) {
@@ -181,7 +190,21 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   const int64_t cap = std::max<int64_t>(opts->max_events, 1);
   if (cap >= (int64_t(1) << 31)) return cleanup(fail(CEP_E_ARG, "max_events must be < 2^31 per batch"));
   if (s->scal.ensure(64) || hipMemset(s->scal.p, 0, 64)) return cleanup(fail(CEP_E_HIP, "device allocation failed"));
-  if (sp && path != CEP_PATH_GENERAL) {
+  if (follow) {
+    // the rows of a stencil session without carry (a start completes at most once: cap rows), and the
+    // bitmaps of follow.hip for a batch of max_events
+    const StencilProgram& FP = P.follow;
+    const size_t nt = size_t(follow_tiles(cap)), planes = size_t(FP.k) + 1;
+    if (s->prog.ensure(sizeof(StencilProgram)) || s->total.ensure(64) || s->sum.ensure(64) ||
+        s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap)) || s->fw_bits.ensure(planes * nt * 64 * 8) ||
+        s->fw_sum.ensure(planes * nt * 8) || s->fw_tile.ensure(nt * 8) || s->fw_cnt.ensure(nt * 64 * 8) ||
+        s->fw_pre.ensure(nt * 64 * 8) || s->scan_tmp.ensure((nt / 16 + 4) * 8))
+      return cleanup(fail(CEP_E_HIP, "device allocation failed"));
+    s->out_cap = cap;
+    if (hipMemcpy(s->prog.p, &FP, sizeof(StencilProgram), hipMemcpyHostToDevice) || hipMemset(s->total.p, 0, s->total.cap))
+      return cleanup(fail(CEP_E_HIP, "device init failed"));
+  }
+  if (sp && path != CEP_PATH_GENERAL && !follow) {
     const int k = sp->k;
     const int64_t nt = stencil_tiles(cap);
     // a run ends at most once, so a batch has at most one match per start: its records, plus on chain
@@ -337,6 +360,15 @@ int cep_pattern_mask_pass(const cep_pattern* p, int32_t* k, int32_t* chain) {
   return CEP_OK;
 }
 
+int cep_pattern_follow(const cep_pattern* p, int32_t* k, uint32_t* next_mask) {
+  if (!p) return fail(CEP_E_ARG, "null argument");
+  const Program& P = p->prog;
+  if (!P.follow_ok) return fail(CEP_E_UNSUPPORTED, "follow path does not apply: " + P.follow_why);
+  if (k) *k = P.follow.k;
+  if (next_mask) *next_mask = P.follow_next;
+  return CEP_OK;
+}
+
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed) {
   if (!p || !needed) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
@@ -368,8 +400,8 @@ static int push_dispatch(cep_session* s, const cep_batch* b, hipStream_t st, boo
 int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   if (!s || !b) return fail(CEP_E_ARG, "null argument");
   static const char* const kRange[] = {"cep_push_batch", "cep_push_batch:stencil", "cep_push_batch:general",
-                                       "cep_push_batch:chain", "cep_push_batch:runs"};
-  RoctxRange range(kRange[s->path >= 1 && s->path <= 4 ? s->path : 0]);
+                                       "cep_push_batch:chain", "cep_push_batch:runs", "cep_push_batch:follow"};
+  RoctxRange range(kRange[s->path >= 1 && s->path <= 5 ? s->path : 0]);
   const Program& P = s->pat->prog;
   if (b->n < 0 || b->n > s->opts.max_events) return fail(CEP_E_ARG, "batch larger than the session capacity");
   if (b->n > 0 && !b->key_id) return fail(CEP_E_ARG, "key_id is required");
@@ -389,9 +421,9 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
   if ((b->flags & CEP_BATCH_FILTER) && !s->carry)
     return fail(CEP_E_UNSUPPORTED, "CEP_BATCH_FILTER needs a CEP_SESSION_CARRY session");
   if ((b->flags & CEP_BATCH_STOP_AT_ERROR) && s->path != CEP_PATH_GENERAL && stencil_batch) {
-    static const char* const kPath[] = {"", "stencil", "", "chain", "runs"};
+    static const char* const kPath[] = {"", "stencil", "", "chain", "runs", "follow"};
     return fail(CEP_E_UNSUPPORTED, std::string("CEP_BATCH_STOP_AT_ERROR is for general-path batches: this batch runs on "
-                                               "the ") + kPath[s->path >= 1 && s->path <= 4 ? s->path : 0] +
+                                               "the ") + kPath[s->path >= 1 && s->path <= 5 ? s->path : 0] +
                                        " path (bounded work per record, no runaway keys)");
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -453,7 +485,11 @@ static int push_dispatch(cep_session* s, const cep_batch* b, hipStream_t st, boo
     s->last_path = CEP_PATH_RUNS;
     return push_runs(s, b, st);
   }
-  if (s->path != CEP_PATH_GENERAL && s->path != CEP_PATH_RUNS && stencil_batch) {
+  if (s->path == CEP_PATH_FOLLOW && stencil_batch) {
+    s->last_path = CEP_PATH_FOLLOW;
+    return push_follow(s, b, st);
+  }
+  if (s->path != CEP_PATH_GENERAL && s->path != CEP_PATH_RUNS && s->path != CEP_PATH_FOLLOW && stencil_batch) {
     s->last_path = s->path;
     return push_stencil(s, b, st);
   }
@@ -722,6 +758,8 @@ int cep_collect(cep_session* s, cep_matches* o) {
 int64_t cep_batch_id(const cep_session* s) { return s ? s->push_id : -1; }
 
 int32_t cep_filter_tile_records(void) { return FILTER_TF; }
+
+int32_t cep_follow_tile_records(void) { return FOLLOW_TILE; }
 
 // the delivery buffer holding batch `id`, or -1
 static int delivered_slot(const cep_session* s, int64_t id) {

@@ -456,6 +456,20 @@ bool stencil_shape(const Program& P, uint32_t& opt, std::string& why) {
   return true;
 }
 
+// predicate slot `slot` of S: the terms of a lowered predicate (at most STENCIL_MAX_TERMS)
+void put_slot(StencilProgram& S, int slot, const DNF& d) {
+  S.nterms[slot] = int(d.size());
+  S.pslots |= 1 << slot;
+  for (size_t t = 0; t < d.size(); t++) {
+    const Term& tm = d[t];
+    S.vi[slot][t] = tm.has_v ? StencilAtomI{tm.v.lo, tm.v.hi} : StencilAtomI{IMIN, IMAX};
+    S.vf[slot][t] = tm.has_v ? StencilAtomF{tm.v.dlo, tm.v.dhi} : StencilAtomF{-INFINITY, INFINITY};
+    S.tp[slot][t] = tm.has_t ? StencilAtomI{tm.t.lo, tm.t.hi} : StencilAtomI{IMIN, IMAX};
+    S.hasv[slot][t] = tm.has_v ? 1 : 0;
+    if (tm.has_t) S.use_topic = 1;
+  }
+}
+
 void analyse_stencil(Program& P) {
   auto no = [&](const std::string& w) { P.stencil_ok = false; P.stencil_why = w; };
   const int k = int(P.pats.size());
@@ -474,16 +488,7 @@ void analyse_stencil(Program& P) {
     DNF d = L.lower(pred, false);
     if (!L.ok) return;
     if (d.size() > STENCIL_MAX_TERMS) { L.fail("too many terms"); return; }
-    S.nterms[slot] = int(d.size());
-    S.pslots |= 1 << slot;
-    for (size_t t = 0; t < d.size(); t++) {
-      const Term& tm = d[t];
-      S.vi[slot][t] = tm.has_v ? StencilAtomI{tm.v.lo, tm.v.hi} : StencilAtomI{IMIN, IMAX};
-      S.vf[slot][t] = tm.has_v ? StencilAtomF{tm.v.dlo, tm.v.dhi} : StencilAtomF{-INFINITY, INFINITY};
-      S.tp[slot][t] = tm.has_t ? StencilAtomI{tm.t.lo, tm.t.hi} : StencilAtomI{IMIN, IMAX};
-      S.hasv[slot][t] = tm.has_v ? 1 : 0;
-      if (tm.has_t) S.use_topic = 1;
-    }
+    put_slot(S, slot, d);
   };
   for (int i = 0; i < k && L.ok; i++) {
     const auto& p = P.pats[i];
@@ -589,6 +594,63 @@ void analyse_runs(Program& P) {
   }
   P.runs_ok = true;
   P.runs_why.clear();
+}
+
+// ---------------------------------------------------------------- skip-till-next walks (follow path)
+// A skip-till-next stage's IGNORE edge is NOT of exactly the predicate its BEGIN edge tests
+// (build_stages above), so with nothing but strict and skip-till-next stages of cardinality ONE / times(n)
+// no edge combination branches (NFA.java:392-397): a run started at record j0 is one deterministic walk --
+// a strict slot takes the next record of the key or the run dies, a skip-till-next slot the key's next
+// record satisfying it -- and emits at most one match.  The slots (a times(n) stage is n of them) are
+// lowered as analyse_stencil lowers stages; bit s of follow_next: slot s is skip-till-next.
+void analyse_follow(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_ok = false; P.follow_why = w; };
+  StencilProgram& S = P.follow;
+  memset(&S, 0, sizeof S);
+  P.follow_next = 0;
+  const int np = int(P.pats.size());
+  int K = 0;
+  bool any_next = false;
+  for (int i = 0; i < np; i++) {
+    const auto& p = P.pats[i];
+    if (p.one_or_more) return no(p.optional ? "zeroOrMore stage" : "oneOrMore stage");
+    if (p.optional) return no("optional stage");
+    if (!p.folds.empty()) return no("fold");
+    for (int j = 0; j < i; j++)
+      if (P.pats[j].name_id == p.name_id) return no("duplicate stage names");
+    if (p.strategy == S_ANY) return no("skip-till-any stage");
+    if (p.strategy != S_STRICT && p.strategy != S_NEXT) return no("unknown selection strategy");
+    if (i == 0 && p.strategy != S_STRICT) return no("non-strict first stage");
+    if (i == 0 && p.times > 1) return no("times on the first stage");
+    if (p.times < 1) return no("times below 1");
+    K += p.times;
+    if (K > STENCIL_MAX_K) return no("more than 8 slots (stages, a times(n) stage counting n)");
+    any_next = any_next || p.strategy == S_NEXT;
+  }
+  if (!any_next)
+    return no(std::string("no skip-till-next stage: ") + (P.stencil_ok ? "the stencil path takes the pattern"
+                                                          : P.runs_ok  ? "the runs path takes the pattern"
+                                                                       : "the pattern keeps its path"));
+  Lowering L;
+  S.k = K;
+  for (int i = 0, slot = 0; i < np && L.ok; i++) {
+    const auto& p = P.pats[i];
+    DNF d = L.lower(p.topic >= 0 ? mk(OP_AND, mk_topic(p.topic), p.pred) : p.pred, false);
+    if (L.ok && d.size() > STENCIL_MAX_TERMS) L.fail("too many terms");
+    if (!L.ok) break;
+    for (int r = 0; r < p.times; r++, slot++) {
+      S.name[slot] = p.name_id;
+      put_slot(S, slot, d);
+      if (p.strategy == S_NEXT) P.follow_next |= 1u << slot;
+    }
+  }
+  if (!L.ok) return no(L.why);
+  if (L.col < 0) { L.col = 0; L.coltype = P.coltypes.empty() ? T_I32 : P.coltypes[0]; }
+  S.col = L.col;
+  S.coltype = L.coltype;
+  if (!build_table(S)) return no("predicates cut the value axis into more than 16 intervals");
+  P.follow_ok = true;
+  P.follow_why.clear();
 }
 
 // ---------------------------------------------------------------- bytecode
@@ -962,6 +1024,7 @@ int compile_ir(const uint8_t* ir, size_t len, Program& P, std::string& err) {
   P.general_ok = lower_general(P, P.general_why) == CEP_OK;
   analyse_runs(P);
   analyse_mask_pass(P);
+  analyse_follow(P);
   P.has_seq = false;
   for (const auto& pd : P.pats) {
     P.has_seq = P.has_seq || uses_seq(pd.pred);

@@ -127,6 +127,13 @@ struct Program {
   std::string mask_why;
   StencilProgram mask_stencil{};
   MaskProgram mask_prog{};
+  // follow form (compile.cpp analyse_follow; CEP_SESSION_FOLLOW sessions, CEP_PATH_FOLLOW): strict and
+  // skip-till-next stages of cardinality ONE / times(n), each run one deterministic walk -- the expanded
+  // slots lowered like stencil stages (k = slots, chain = 0), bit s of follow_next: slot s is skip-till-next
+  bool follow_ok = false;
+  std::string follow_why;
+  StencilProgram follow{};
+  uint32_t follow_next = 0;
 };
 
 // ---- carried state of the stencil / chain paths (CEP_SESSION_CARRY) ----

@@ -189,6 +189,35 @@ hipError_t stencil_resolve_launch(const int32_t* key, const int32_t* out, int k,
 hipError_t stencil_deliver_launch(const int32_t* key, const int32_t* out, int k, const int64_t* total, int64_t out_cap,
                                   const StencilCarry& C, const DeliverArgs& D, hipStream_t st);
 
+// ---- follow.hip: the follow path (CEP_PATH_FOLLOW), skip-till-next walks over per-slot bitmaps ----
+constexpr int FOLLOW_TILE = 4096;                 // records per workgroup of follow_bits: 64 bitmap words
+struct FollowArgs {
+  const int32_t* key;
+  const void* val;
+  const int32_t* topic;
+  int64_t n;
+  const StencilProgram* prog_dev;   // the pattern's slots (Program::follow)
+  int k, coltype, use_topic;
+  uint32_t next_mask;               // bit s: slot s is skip-till-next (Program::follow_next)
+  // per tile t = follow_tiles(n): bits (k + 1) x 64 t words (slot-major, then the key starts), sum (k + 1) x t
+  // words (bit w % 64 of word w / 64: bits word w is not zero), tile_starts t words (slot 0's set bits)
+  unsigned long long* bits;
+  unsigned long long* sum;
+  int64_t* tile_starts;
+  int64_t* wcnt;                    // 64 t words: completed walks per word of slot 0's bitmap
+  int64_t* wpre;                    // their exclusive prefix
+  int64_t* scan_tmp;                // t / 16 + 4 words
+  int64_t* nm;                      // device: completed walks
+  unsigned long long* max_span;     // device: the longest last record - start
+  unsigned long long* keys;         // the completed walks in start order, (last record << 31) | start
+};
+int64_t follow_tiles(int64_t n);
+hipError_t follow_bits_launch(const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
+hipError_t follow_count_launch(const FollowArgs& A, hipStream_t st);
+hipError_t follow_write_launch(const FollowArgs& A, hipStream_t st);
+hipError_t follow_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int32_t* out,
+                              int64_t* total, hipStream_t st);
+
 // ---- masks.hip: the mask pre-pass of CEP_SESSION_MASK_PASS sessions (jf: the per-pattern kernel, or null) ----
 hipError_t masks_launch(const MaskArgs& A, hipStream_t st, hipFunction_t jf);
 

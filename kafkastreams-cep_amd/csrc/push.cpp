@@ -584,6 +584,78 @@ int push_runs(cep_session* s, const cep_batch* b, hipStream_t st) {
   return CEP_OK;
 }
 
+// Skip-till-next walks (follow.hip): the slots' bitmaps in one streaming pass, the completed walks counted
+// and compacted in start order, ordered by (completing record, start) as the runs path orders its runs, then
+// written as K-int rows -- from there the batch is a finished stencil batch without carry (cep_collect).
+int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
+  const Program& P = s->pat->prog;
+  const StencilProgram& SP = P.follow;
+  const int64_t n = b->n;
+  NfaArgs in{};
+  int rc = stage_inputs(s, b, st, in, true);
+  if (rc) return rc;
+  s->d_key = in.key;
+  if (n == 0) {
+    HIPCHECK(hipMemsetAsync(s->total.p, 0, 8, st));
+    return push_empty(s, st, true);
+  }
+  const void* col = b->n_cols ? in.cols[SP.col] : nullptr;
+  const int32_t* topic = SP.use_topic ? in.topic : nullptr;
+  if (SP.use_topic && !topic) {                    // no topic column: every record on topic id 0
+    if (s->h_topic.ensure(size_t(n) * 4)) return fail(CEP_E_HIP, "staging allocation failed");
+    HIPCHECK(hipMemsetAsync(s->h_topic.p, 0, size_t(n) * 4, st));
+    topic = s->h_topic.as<int32_t>();
+  }
+  if (!col) return fail(CEP_E_ARG, "null value column");
+  if ((reinterpret_cast<uintptr_t>(in.key) | reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(topic)) & 15)
+    return fail(CEP_E_ARG, "device columns must be 16-byte aligned");
+  const int64_t nt = follow_tiles(n);
+  if (size_t(nt) * 64 * size_t(SP.k + 1) * 8 > s->fw_bits.cap) return fail(CEP_E_ARG, "batch larger than the session capacity");
+  if (s->scan_tmp.ensure(size_t(nt / 16 + 4) * 8)) return fail(CEP_E_HIP, "allocation failed");
+  int64_t* scal = s->scal.as<int64_t>();
+  FollowArgs A{};
+  A.key = in.key; A.val = col; A.topic = topic; A.n = n;
+  A.prog_dev = s->prog.as<StencilProgram>();
+  A.k = SP.k; A.coltype = SP.coltype; A.use_topic = SP.use_topic; A.next_mask = P.follow_next;
+  A.bits = s->fw_bits.as<unsigned long long>();
+  A.sum = s->fw_sum.as<unsigned long long>();
+  A.tile_starts = s->fw_tile.as<int64_t>();
+  A.wcnt = s->fw_cnt.as<int64_t>();
+  A.wpre = s->fw_pre.as<int64_t>();
+  A.scan_tmp = s->scan_tmp.as<int64_t>();
+  A.nm = scal + 4;
+  A.max_span = reinterpret_cast<unsigned long long*>(scal + 5);
+  HIPCHECK(follow_bits_launch(A, s->timing ? s->ev0.e : nullptr, s->timing ? s->ev1.e : nullptr, st));
+  HIPCHECK(follow_count_launch(A, st));
+  // the batch's one host synchronisation: the completed walks and their longest span
+  int64_t h[2] = {0, 0};
+  HIPCHECK(hipMemcpyAsync(h, scal + 4, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  const int64_t nm = h[0], span = h[1];
+  if (nm < 0 || nm > n) return fail(CEP_E_RUN_CAPACITY, "more completed walks than records");
+  if (nm > 0) {
+    int bits = 1;                                  // bits of the completing record
+    while ((int64_t(1) << bits) <= n) bits++;
+    const bool ranked = span <= 1024 && !getenv_flag("KCEP_RUNS_RADIX");
+    size_t tmp_bytes = 0;
+    if (!ranked) HIPCHECK(runs_sort(nullptr, nullptr, nm, bits, nullptr, &tmp_bytes, st));
+    if (s->rk.ensure(size_t(nm) * 8) || s->rk_sorted.ensure(size_t(nm) * 8) ||
+        (ranked ? s->r_len.ensure(size_t(nm) * 8) : s->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16))))
+      return fail(CEP_E_HIP, "allocation failed");
+    A.keys = s->rk.as<unsigned long long>();
+    HIPCHECK(follow_write_launch(A, st));
+    // (completing record, start) order: the runs path's windowed rank when every walk spans <= 1024
+    // records, else its radix sort over the completing record's bits
+    if (ranked)
+      HIPCHECK(runs_order_launch(A.keys, nm, int(span), s->rk_sorted.as<unsigned long long>(), s->r_len.as<int64_t>(), st));
+    else
+      HIPCHECK(runs_sort(A.keys, s->rk_sorted.as<unsigned long long>(), nm, bits, s->rk_tmp.p, &tmp_bytes, st));
+  }
+  HIPCHECK(follow_rows_launch(A, s->rk_sorted.as<unsigned long long>(), nm, s->out.as<int32_t>(), s->total.as<int64_t>(), st));
+  if (s->timing) HIPCHECK(hipEventRecord(s->eb1, st));
+  return CEP_OK;
+}
+
 int push_general(cep_session* s, const cep_batch* b, hipStream_t st) {
   const Program& P = s->pat->prog;
   const int64_t n = b->n;

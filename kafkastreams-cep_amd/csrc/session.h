@@ -121,6 +121,10 @@ struct cep_session {
   int64_t out_cap = 0;
   const int32_t* d_key = nullptr;
   DBuf mprog, mcol;             // mask pass: the MaskProgram; the mask column (max_events rounded up to 4 int32)
+  // ---- follow path (follow.hip; prog, out, total, sum as above): the slots' bitmaps and their second level,
+  // the tiles' starts, the completed walks per bitmap word and their prefix, sized from max_events at open;
+  // the walks' keys, their order and the sort's scratch are the runs workspace's rk, rk_sorted, r_len, rk_tmp ----
+  DBuf fw_bits, fw_sum, fw_tile, fw_cnt, fw_pre;
   // ---- staging of host-resident batches (stage_host): a pinned ring the caller's columns are copied
   // into in chunks, each chunk moved by one async copy into one packed device image; caller memory
   // that is itself pinned is copied from directly and the push waits for that copy ----
@@ -267,6 +271,7 @@ inline bool halo_session(const cep_session* s) { return s->carry && (s->path == 
 void dl_layout(const cep_session* s, int slot, int64_t*& hdr, int32_t*& hkey, int64_t*& hpos);
 int push_stencil(cep_session* s, const cep_batch* b, hipStream_t st);
 int push_runs(cep_session* s, const cep_batch* b, hipStream_t st);
+int push_follow(cep_session* s, const cep_batch* b, hipStream_t st);
 int push_general(cep_session* s, const cep_batch* b, hipStream_t st);
 int group_batch(cep_session* s, const cep_batch* b, hipStream_t st, cep_batch& gb, const void** gcols);
 int arrival_csr(cep_session* s, int64_t base, int64_t n, hipStream_t st);

@@ -24,6 +24,7 @@ ERRORS = {
 E_RUN_CAPACITY = 9         # a key over its device workspace, handed back per key (cep_batch_errors)
 MODE_NFA, MODE_PROCESSOR = 0, 1
 PATH_STENCIL, PATH_GENERAL, PATH_CHAIN, PATH_RUNS = 1, 2, 3, 4
+PATH_FOLLOW = 5            # skip-till-next walks (SESSION_FOLLOW, CompiledPattern.follow)
 MEM_HOST, MEM_DEVICE = 0, 1
 BATCH_OFFSETS_MONOTONE = 1
 BATCH_DELIVER = 2          # the push is collected at once: matches handed to pinned host memory by the device
@@ -37,6 +38,7 @@ SESSION_PROFILE = 4
 SESSION_LANE_NFA = 8
 SESSION_WAVE_NFA = 16
 SESSION_MASK_PASS = 32     # opt-in: stencil / chain path for eligible multi-column predicates (CompiledPattern.mask_pass)
+SESSION_FOLLOW = 64        # opt-in: the follow path for eligible skip-till-next patterns (CompiledPattern.follow)
 
 
 class CepError(RuntimeError):
@@ -83,7 +85,7 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_match_count_to", "cep_state_evict", "cep_state_import_keys", "cep_state_positions",
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
            "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped",
-           "cep_filter_tile_records", "cep_pattern_mask_pass"]
+           "cep_filter_tile_records", "cep_pattern_mask_pass", "cep_pattern_follow", "cep_follow_tile_records"]
 
 _lib = None
 
@@ -148,6 +150,10 @@ def lib():
         L.cep_filter_tile_records.restype = C.c_int32
     if hasattr(L, "cep_pattern_mask_pass"):     # (KCEP_LIB A/B runs may load an older build)
         L.cep_pattern_mask_pass.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(L, "cep_pattern_follow"):        # (KCEP_LIB A/B runs may load an older build)
+        L.cep_pattern_follow.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+        L.cep_follow_tile_records.argtypes = []
+        L.cep_follow_tile_records.restype = C.c_int32
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -179,6 +185,11 @@ def check(rc: int):
 def filter_tile_records() -> int:
     """cep_filter_tile_records: records per workgroup of BATCH_FILTER's admission scan."""
     return int(lib().cep_filter_tile_records())
+
+
+def follow_tile_records() -> int:
+    """cep_follow_tile_records: records per workgroup of the follow path's streaming bitmap kernel."""
+    return int(lib().cep_follow_tile_records())
 
 
 def state_positions(blob: bytes) -> np.ndarray:
@@ -237,6 +248,17 @@ class CompiledPattern:
             return True, k.value, bool(chain.value), ""
         return False, 0, False, lib().cep_last_error().decode()
 
+    @property
+    def follow(self):
+        """cep_pattern_follow: ``(ok, k, next_mask, why)`` -- whether a ``follow=True`` session (or
+        ``force_path=PATH_FOLLOW``) runs the pattern on the follow path, its slots (a ``times(n)`` stage
+        counts n), the mask of the skip-till-next slots, and the reason when it does not."""
+        k, nxt = C.c_int32(), C.c_uint32()
+        rc = lib().cep_pattern_follow(self.h, C.byref(k), C.byref(nxt))
+        if rc == CEP_OK:
+            return True, k.value, nxt.value, ""
+        return False, 0, 0, lib().cep_last_error().decode()
+
     def kernel_source(self, path=PATH_RUNS) -> str:
         """HIP source of the kernels compiled for this pattern (cep_pattern_kernel_source)."""
         n = C.c_size_t()
@@ -266,7 +288,7 @@ class Session:
 
     def __init__(self, pattern: CompiledPattern, max_events: int, mode=MODE_PROCESSOR, device=0, force_path=0,
                  carry=False, max_keys=0, interpret=False, profile=False, max_key_words=0, lane_nfa=None,
-                 max_pool_bytes=0, mask_pass=False):
+                 max_pool_bytes=0, mask_pass=False, follow=False):
         """``carry=True``: every key's NFA state continues across batches (CEP_SESSION_CARRY);
         key ids must then be dense in [0, max_keys) and record positions are stream positions.
         ``interpret=True``: the built-in interpreting kernels instead of kernels compiled for the
@@ -276,13 +298,17 @@ class Session:
         how far the general path's workspace pool may grow for a batch (0: a quarter of the HBM).
         ``mask_pass=True`` (CEP_SESSION_MASK_PASS): a strict pattern whose predicates read several
         columns, arithmetic or event metadata (``CompiledPattern.mask_pass``) opens on the stencil / chain
-        path, a pre-pass kernel writing each record's stage mask; no effect on any other pattern."""
+        path, a pre-pass kernel writing each record's stage mask; no effect on any other pattern.
+        ``follow=True`` (CEP_SESSION_FOLLOW): a pattern of strict and skip-till-next stages
+        (``CompiledPattern.follow``) opens on the follow path instead of the general NFA; no effect on any
+        other pattern, nor with ``carry=True``."""
         self.pattern = pattern
         self.h = C.c_void_p()
         # lane_nfa: None = the library's choice, True = one key per lane, False = one key per wave
         flags = ((SESSION_CARRY if carry else 0) | (SESSION_INTERPRET if interpret else 0) |
                  (SESSION_PROFILE if profile else 0) | (SESSION_LANE_NFA if lane_nfa else 0) |
-                 (SESSION_WAVE_NFA if lane_nfa is False else 0) | (SESSION_MASK_PASS if mask_pass else 0))
+                 (SESSION_WAVE_NFA if lane_nfa is False else 0) | (SESSION_MASK_PASS if mask_pass else 0) |
+                 (SESSION_FOLLOW if follow else 0))
         o = Opts(device, mode, force_path, flags, max_events, max_keys, 0.0, max_key_words, max_pool_bytes)
         check(lib().cep_session_open(pattern.h, C.byref(o), C.byref(self.h)))
         self.path = lib().cep_session_path(self.h)
