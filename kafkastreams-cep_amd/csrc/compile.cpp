@@ -410,14 +410,25 @@ bool build_table(StencilProgram& S) {
   S.lut_n = 0;
   S.lut_lo = 0;
   memset(S.lut, 0, sizeof S.lut);
-  // (worth it from ~6 breakpoints: C5's 8 -> kernel -2 %, C2's 4 -> +0.5 %, profiles/r02_ab_c2_c5_lut.log)
-  if (!isf && S.ntbp == 0 && nb >= 6 && bi.back() - bi.front() < int64_t(sizeof S.lut)) {
+  // The dense table whenever it fits: the look-up is one clamp, one subtract and one LDS read per record
+  // (stencil_kernel.h masks_of_chunk), fewer instructions than one breakpoint's compare-and-count on an
+  // int32 column, so it is taken from the first breakpoint on.  (The earlier form -- a 64-bit subtract
+  // and two range branches around the read -- paid only from ~6 breakpoints: profiles/r02_ab_c2_c5_lut.log;
+  // C2's 4 breakpoints on this form: profiles/plain_valu_ab.jsonl.)  An int64 column clamps by two 64-bit
+  // compares and selects, five instructions against two per breakpoint: from 3 breakpoints.
+  // It fits when the breakpoints span < STENCIL_LUT_MAX values and both clamp bounds, lut_lo - 1 and
+  // lut_lo + lut_n, are values of the column's type; otherwise the breakpoint arm stays.
+  const int64_t tmin = S.coltype == T_I32 ? int64_t(INT32_MIN) : IMIN, tmax = S.coltype == T_I32 ? int64_t(INT32_MAX) : IMAX;
+  if (!isf && S.ntbp == 0 && nb >= (S.coltype == T_I32 ? 1 : 3) && uint64_t(bi.back()) - uint64_t(bi.front()) < uint64_t(STENCIL_LUT_MAX) &&
+      bi.front() > tmin && bi.back() < tmax) {
     S.lut_lo = bi.front();
     S.lut_n = int32_t(bi.back() - bi.front() + 1);
+    S.lut[0] = S.table[0];
     for (int r = 0, iv = 0; r < S.lut_n; r++) {   // iv = #{breakpoints <= lut_lo + r}
       while (iv < nb && bi[iv] <= S.lut_lo + r) iv++;
-      S.lut[r] = S.table[iv];
+      S.lut[1 + r] = S.table[iv];
     }
+    S.lut[1 + S.lut_n] = S.table[nb];
   }
   return true;
 }
@@ -876,7 +887,7 @@ void analyse_mask_pass(Program& P) {
   S.coltype = T_I32;
   S.lut_lo = 0;
   S.lut_n = 256;
-  for (int m = 0; m < 256; m++) S.lut[m] = uint8_t(m);
+  for (int m = 0; m < 256; m++) S.lut[1 + m] = uint8_t(m);   // (lut[0] and lut[257], outside the range: no stage)
   P.mask_ok = true;
   P.mask_why.clear();
 }

@@ -91,17 +91,14 @@ __global__ __launch_bounds__(ST_THREADS) void follow_bits(const int32_t* __restr
                                                          int64_t nt, int64_t* __restrict__ tile_starts) {
   __shared__ __attribute__((aligned(16))) uint8_t s_mask[ST_TILE];   // the records' stage masks
   __shared__ __attribute__((aligned(16))) uint8_t s_ks[ST_TILE];     // 1: the record starts a key segment
-  __shared__ uint8_t s_tab[64];
-  __shared__ uint8_t s_lut[256];
-  __shared__ uint8_t s_nan[4];
+  __shared__ MaskTables<VT> s_mt;
   __shared__ uint32_t s_part[STENCIL_MAX_K + 1][ST_THREADS / 64];    // per plane and wave: its 16 words' not-zero bits
   __shared__ int32_t s_cnt[ST_THREADS / 64];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
-  if (tid < 64) s_tab[tid] = P->table[tid];
-  s_lut[tid] = P->lut[tid];                       // (ST_THREADS == 256 entries)
-  if (tid < 4) s_nan[tid] = P->nan_mask[tid];
+  load_tables<VT>(s_mt, P, tid);
+  const MaskUni<VT> U = load_uni<VT>(P);
   const int64_t tile = blockIdx.x;
   const int64_t base = tile * ST_TILE;
 
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(ST_THREADS) void follow_bits(const int32_t* __restr
   }
   __syncthreads();                                // the tables
   uint32_t packed[4];
-  masks_of_chunk<VT, TOPIC>(cur, P, s_tab, s_nan, packed, s_lut);
+  masks_of_chunk<VT, TOPIC>(cur, P, s_mt, U, packed);
 #pragma unroll
   for (int q = 0; q < ST_EPT / 4; q++) {
     const int local = q * (ST_THREADS * 4) + tid * 4;

@@ -69,6 +69,7 @@ struct StencilAtomF { double lo, hi; };
 // the SKIP_PROCEED edge of optional stage i: the successor's predicate without
 // its topic filter (StagesFactory.java:159-169); the edge is that AND NOT slot i.
 constexpr int CHAIN_MAX_K = 4;
+constexpr int STENCIL_LUT_MAX = 256;   // values a dense mask table spans at most
 struct StencilProgram {
   int32_t k;
   int32_t col;                       // value column read by every predicate
@@ -94,12 +95,14 @@ struct StencilProgram {
   int32_t tbp[3];
   uint8_t table[64];
   uint8_t nan_mask[4];               // double columns: mask of a NaN value per topic interval
-  // Dense form of the same table for integer columns without topic atoms with >= 6 breakpoints spanning
-  // < 256 values: mask = lut[v - lut_lo] inside [lut_lo, lut_lo + lut_n), table[0] below,
-  // table[nbp] above (one LDS read per record instead of nbp compares); lut_n = 0: not used
+  // Dense form of the same table for integer columns without topic atoms whose breakpoints span
+  // < STENCIL_LUT_MAX values (compile.cpp build_table): the mask of v is lut[clamp(v, lut_lo - 1,
+  // lut_lo + lut_n) - (lut_lo - 1)], one clamp and one LDS read per record instead of nbp compares.
+  // lut[0] = table[0] (below the range), lut[1 + r] = the mask of lut_lo + r, lut[1 + lut_n] =
+  // table[nbp] (above); both clamp bounds are values of the column's type.  lut_n = 0: not used
   int64_t lut_lo;
   int32_t lut_n;
-  uint8_t lut[256];
+  uint8_t lut[STENCIL_LUT_MAX + 8];  // lut_n + 2 entries in use
 };
 
 struct Program {

@@ -6,7 +6,7 @@
 // per-record stage-mask byte; where the predicates do not lower to intervals of one column
 // (compile.cpp analyse_stencil), this pass evaluates them per record through the shared bytecode
 // machinery (interp.h) and writes the mask as an int32 column, which those kernels then read as their
-// value column through the identity table (StencilProgram.lut[m] = m).
+// value column through the identity table (StencilProgram.lut[1 + m] = m).
 //
 // The built-in kernel here interprets; jit.cpp compiles the same body (masks_dev.h) per pattern.
 #include <hip/hip_runtime.h>

@@ -129,48 +129,107 @@ __device__ __forceinline__ void load_chunk(Chunk<VT, TOPIC>& c, const int32_t* _
   }
 }
 
-// interval index of a value: number of breakpoints <= v (breakpoints uniform, in SGPRs)
+// ---- a record's stage mask ----
+// The program's tables sit in LDS, filled once per workgroup (load_tables, then a barrier), and the
+// numbers a look-up needs are read once into SGPRs (MaskUni, load_uni): a tile's masks then cost no
+// scalar load and no wait on the scalar cache.
 template <class VT>
 __device__ __forceinline__ VT bp_at(const StencilProgram* __restrict__ P, int b) {
   if constexpr (std::is_same<VT, double>::value) return P->bpf[b];
   else return VT(P->bpi[b]);
 }
 
+// breakpoints per round of the breakpoint arm (masks_of_chunk); 4 take the C2 kernel to 75 VGPRs, its
+// 7th wave gone, and put 12 B of scratch into the i32 topic variant, 2 leave both as they were
+constexpr int ST_BPG = 2;
+template <class VT>
+struct MaskTables {
+  uint8_t tab[64];                                // StencilProgram::table
+  uint8_t lut[STENCIL_LUT_MAX + 8];               // StencilProgram::lut: below, the range, above
+  uint8_t nan[4];
+  __attribute__((aligned(16))) VT bp[16];         // the value breakpoints, read ST_BPG at a time ([15]: never used)
+};
+template <class VT>
+struct MaskUni {
+  int nbp, ntbp, lut_n;
+  VT lo1, hi;                                     // the dense table's clamp bounds lut_lo - 1, lut_lo + lut_n
+};
+
+template <class VT>
+__device__ __forceinline__ void load_tables(MaskTables<VT>& T, const StencilProgram* __restrict__ P, int tid) {
+  static_assert(ST_THREADS == STENCIL_LUT_MAX, "one dense-table entry per thread, the padding by the first 8");
+  if (tid < 64) T.tab[tid] = P->table[tid];
+  T.lut[tid] = P->lut[tid];
+  if (tid < 8) T.lut[STENCIL_LUT_MAX + tid] = P->lut[STENCIL_LUT_MAX + tid];
+  if (tid < 4) T.nan[tid] = P->nan_mask[tid];
+  if (tid < 16) T.bp[tid] = tid < 15 ? bp_at<VT>(P, tid) : VT(0);
+}
+template <class VT>
+__device__ __forceinline__ MaskUni<VT> load_uni(const StencilProgram* __restrict__ P) {
+  MaskUni<VT> U{P->nbp, P->ntbp, 0, VT(0), VT(0)};
+  if constexpr (!std::is_same<VT, double>::value) {
+    U.lut_n = P->lut_n;
+    U.lo1 = VT(P->lut_lo - 1);                    // both representable in VT (compile.cpp build_table)
+    U.hi = VT(P->lut_lo + P->lut_n);
+  }
+  return U;
+}
+
+// index of v in the padded dense table: 0 below the range, lut_n + 1 above, no branch
+template <class VT>
+__device__ __forceinline__ uint32_t lut_index(VT v, const MaskUni<VT>& U) {
+  if constexpr (sizeof(VT) == 4) {
+    int32_t c;                                    // (min(max()) of two SGPR bounds is not folded into one med3)
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(c) : "v"(v), "s"(U.lo1), "v"(U.hi));
+    return uint32_t(c) - uint32_t(U.lo1);
+  } else {
+    const VT c = v < U.lo1 ? U.lo1 : v > U.hi ? U.hi : v;
+    return uint32_t(uint64_t(c)) - uint32_t(uint64_t(U.lo1));   // (the difference is < 2^9: the low words do)
+  }
+}
+
 template <class VT, bool TOPIC>
 __device__ __forceinline__ void masks_of_chunk(const Chunk<VT, TOPIC>& c, const StencilProgram* __restrict__ P,
-                                               const uint8_t* s_tab, const uint8_t* s_nan, uint32_t (&packed)[4],
-                                               const uint8_t* s_lut) {
+                                               const MaskTables<VT>& T, const MaskUni<VT>& U, uint32_t (&packed)[4]) {
   if constexpr (!TOPIC && !std::is_same<VT, double>::value) {
-    const int32_t lut_n = P->lut_n;
-    if (lut_n > 0) {                               // dense table: one LDS byte per record (uniform branch)
-      const int64_t lo = P->lut_lo;
-      const uint32_t below = s_tab[0], above = s_tab[P->nbp];
+    if (U.lut_n > 0) {                            // dense table (uniform branch): 16 independent LDS reads, one wait
+      uint32_t m[ST_EPT];
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        uint32_t w = 0;
+      for (int e = 0; e < ST_EPT; e++) m[e] = T.lut[lut_index<VT>(vget<VT>(c.v[e >> 2], e & 3), U)];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int64_t dv = int64_t(vget<VT>(c.v[q], i)) - lo;
-          const uint32_t m = dv < 0 ? below : dv >= lut_n ? above : uint32_t(s_lut[dv]);
-          w |= m << (8 * i);
-        }
-        packed[q] = w;
-      }
+      for (int q = 0; q < 4; q++) packed[q] = m[4 * q] | (m[4 * q + 1] << 8) | (m[4 * q + 2] << 16) | (m[4 * q + 3] << 24);
       return;
     }
   }
+  // interval index of a value: the number of breakpoints <= v.  ST_BPG breakpoints per round come
+  // from LDS together (a broadcast read, moved to SGPRs), each compared with the thread's 16 records
+  // under a uniform guard
   int iv[ST_EPT], it[ST_EPT];
 #pragma unroll
   for (int e = 0; e < ST_EPT; e++) { iv[e] = 0; it[e] = 0; }
-  const int nbp = P->nbp;
-  for (int b = 0; b < nbp; b++) {                 // scalar loop: breakpoint in an SGPR, 16 records per step
-    const VT bp = bp_at<VT>(P, b);
+  for (int b = 0; b < U.nbp; b += ST_BPG) {
+    VT bp[ST_BPG];
 #pragma unroll
-    for (int e = 0; e < ST_EPT; e++) iv[e] += bp <= vget<VT>(c.v[e >> 2], e & 3) ? 1 : 0;
+    for (int u = 0; u < ST_BPG; u++) {
+      if constexpr (sizeof(VT) == 4) {
+        bp[u] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int32_t, T.bp[b + u]));
+      } else {
+        const uint64_t x = __builtin_bit_cast(uint64_t, T.bp[b + u]);
+        const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int32_t(uint32_t(x))));
+        const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int32_t(uint32_t(x >> 32))));
+        bp[u] = __builtin_bit_cast(VT, (uint64_t(hi) << 32) | lo);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < ST_BPG; u++) {
+      if (b + u < U.nbp) {
+#pragma unroll
+        for (int e = 0; e < ST_EPT; e++) iv[e] += bp[u] <= vget<VT>(c.v[e >> 2], e & 3) ? 1 : 0;
+      }
+    }
   }
   if constexpr (TOPIC) {
-    const int ntbp = P->ntbp;
-    for (int b = 0; b < ntbp; b++) {
+    for (int b = 0; b < U.ntbp; b++) {
       const int32_t tb = P->tbp[b];
 #pragma unroll
       for (int e = 0; e < ST_EPT; e++) {
@@ -185,10 +244,10 @@ __device__ __forceinline__ void masks_of_chunk(const Chunk<VT, TOPIC>& c, const 
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int e = 4 * q + i;
-      uint32_t m = s_tab[it[e] * 16 + iv[e]];
+      uint32_t m = T.tab[it[e] * 16 + iv[e]];
       if constexpr (std::is_same<VT, double>::value) {
         const double v = vget<VT>(c.v[q], i);
-        if (v != v) m = s_nan[it[e]];
+        if (v != v) m = T.nan[it[e]];
       }
       w |= m << (8 * i);
     }
@@ -196,23 +255,20 @@ __device__ __forceinline__ void masks_of_chunk(const Chunk<VT, TOPIC>& c, const 
   }
 }
 
+// one record (a halo record), by the same rule
 template <class VT, bool TOPIC>
-__device__ __forceinline__ uint32_t mask_of(const StencilProgram* __restrict__ P, const uint8_t* s_tab,
-                                            const uint8_t* s_nan, VT v, int32_t t, const uint8_t* s_lut) {
+__device__ __forceinline__ uint32_t mask_of(const StencilProgram* __restrict__ P, const MaskTables<VT>& T,
+                                            const MaskUni<VT>& U, VT v, int32_t t) {
   if constexpr (!TOPIC && !std::is_same<VT, double>::value) {
-    const int32_t lut_n = P->lut_n;
-    if (lut_n > 0) {                               // dense table, as masks_of_chunk (uniform branch)
-      const int64_t dv = int64_t(v) - P->lut_lo;
-      return dv < 0 ? s_tab[0] : dv >= lut_n ? s_tab[P->nbp] : s_lut[dv];
-    }
+    if (U.lut_n > 0) return T.lut[lut_index<VT>(v, U)];
   }
   int iv = 0, it = 0;
-  for (int b = 0; b < P->nbp; b++) iv += bp_at<VT>(P, b) <= v ? 1 : 0;
+  for (int b = 0; b < U.nbp; b++) iv += T.bp[b] <= v ? 1 : 0;
   if constexpr (TOPIC)
-    for (int b = 0; b < P->ntbp; b++) it += P->tbp[b] <= t ? 1 : 0;
+    for (int b = 0; b < U.ntbp; b++) it += P->tbp[b] <= t ? 1 : 0;
   if constexpr (std::is_same<VT, double>::value)
-    if (v != v) return s_nan[it];
-  return s_tab[it * 16 + iv];
+    if (v != v) return T.nan[it];
+  return T.tab[it * 16 + iv];
 }
 
 // Chain patterns (strict, optional() stages, K <= 4; compile.cpp analyse_stencil),
@@ -434,17 +490,14 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
   __shared__ __attribute__((aligned(16))) int32_t s_key[ST_KWORDS];   // keys; then the match list
   __shared__ __attribute__((aligned(16))) uint8_t s_mask[ST_TILE + 16];
   __shared__ int32_t s_wsum[SUB][ST_THREADS / 64];
-  __shared__ uint8_t s_tab[64];
-  __shared__ uint8_t s_lut[256];
-  __shared__ uint8_t s_nan[4];
+  __shared__ MaskTables<VT> s_mt;
   __shared__ uint32_t s_super;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
   if (tid == 0) s_super = blockIdx.x;             // no ordering between workgroups is needed
-  if (tid < 64) s_tab[tid] = P->table[tid];
-  s_lut[tid] = P->lut[tid];                       // (ST_THREADS == 256 entries)
-  if (tid < 4) s_nan[tid] = P->nan_mask[tid];
+  load_tables<VT>(s_mt, P, tid);
+  const MaskUni<VT> U = load_uni<VT>(P);
   __syncthreads();
   const int64_t tile0 = int64_t(s_super) * SUB;
   const int ntl = int(ntiles - tile0 < SUB ? ntiles - tile0 : SUB);   // tiles of this workgroup
@@ -533,18 +586,21 @@ __global__ __launch_bounds__(ST_THREADS) void stencil_kernel(
         }
       }
       uint32_t packed[4];
-      masks_of_chunk<VT, TOPIC>(cur, P, s_tab, s_nan, packed, s_lut);
+      masks_of_chunk<VT, TOPIC>(cur, P, s_mt, U, packed);
+      const bool whole = base + ST_TILE <= n;     // uniform: only the batch's last tile masks its tail
 #pragma unroll
       for (int q = 0; q < ST_EPT / 4; q++) {
         const int local = q * (ST_THREADS * 4) + tid * 4;
         uint32_t w = packed[q];
-        const int64_t left = n - (base + local);  // records >= n match nothing
-        if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
+        if (!whole) {
+          const int64_t left = n - (base + local);  // records >= n match nothing
+          if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
+        }
         if constexpr (!CARRY) *reinterpret_cast<v4i*>(&s_key[kpos(16 + local)]) = cur.k[q];
         *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
       }
       if (tid < 16) {                             // halo: the records before the tile (r' = 0..15)
-        if (j == 0 && h_first) h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top, s_lut);
+        if (j == 0 && h_first) h_mask = mask_of<VT, TOPIC>(P, s_mt, U, h_val, h_top);
         if constexpr (!CARRY) s_key[kpos(tid)] = halo_lane ? h_key : INT32_MIN;
         s_mask[tid] = halo_lane ? uint8_t(h_mask) : 0;
       }
@@ -805,6 +861,40 @@ __device__ __forceinline__ void load_tile(Chunk<VT, TOPIC>& c, const int32_t* __
   }
 }
 
+// The window test on the image bytes themselves (the kernel without carry): the thread's 24 window
+// records are six dwords w[0..5], four records each, its own 16 records in w[2..5].  For an own dword D,
+//   hits(D) = AND_s (stage-s bit of the records K-1-s before D's) , each moved to bit 0 of its byte:
+// the records d before D's start 8 d bits lower in {w[D], w[D-1], w[D-2]}, so one funnel shift
+// (v_alignbit_b32) by 8 d less s bits aligns stage s.  Only the four result dwords are compressed to
+// the 16-bit mask (bit i: own record i), by shifts, not by a multiply per stage and qword (byte_bits).
+__device__ __forceinline__ uint32_t win_bits(const uint32_t (&w)[6], int D, int T) {   // 32 bits from bit T of w[D-2] on
+  const int q = T >> 5, r = T & 31;               // (constants once unrolled; zeros past w[D])
+  const uint32_t lo = w[D - 2 + q], hi = q < 2 ? w[D - 1 + q] : 0u;
+  return uint32_t(((uint64_t(hi) << 32) | lo) >> r);
+}
+// bit 0 of the 8 bytes of x, y -> 8 contiguous bits: a bit at 8b (x) or 8b + 4 (y) meets its place
+// 21 + b (25 + b) after the shifts by 0, 7, 14, 21 that two shift-ors make; no two land on one bit
+__device__ __forceinline__ uint32_t lsb_gather(uint32_t x, uint32_t y) {
+  uint32_t z = (x & 0x01010101u) | ((y & 0x01010101u) << 4);
+  z |= z << 7;
+  z |= z << 14;
+  return (z >> 21) & 0xFFu;
+}
+template <int K>
+__device__ __forceinline__ uint32_t window_hits(const uint64_t (&m8)[3]) {
+  uint32_t w[6], a[4];
+#pragma unroll
+  for (int q = 0; q < 3; q++) { w[2 * q] = uint32_t(m8[q]); w[2 * q + 1] = uint32_t(m8[q] >> 32); }
+#pragma unroll
+  for (int D = 2; D < 6; D++) {
+    uint32_t acc = 0xFFFFFFFFu;
+#pragma unroll
+    for (int s = 0; s < K; s++) acc &= win_bits(w, D, 64 - 8 * (K - 1 - s) + s);
+    a[D - 2] = acc;
+  }
+  return lsb_gather(a[0], a[1]) | (lsb_gather(a[2], a[3]) << 8);
+}
+
 // Keys at candidates only (the kernel without carry).  The stage predicates read the value column
 // alone, so the window test first runs on the stage bits: a thread's 16-bit candidate mask.  Only a
 // candidate's window needs keys, and each thread holding one reads them from global memory itself:
@@ -877,7 +967,7 @@ __device__ __forceinline__ uint32_t window_same_keys(const int32_t* __restrict__
 #ifndef ST_PLAIN_WAVES
 #define ST_PLAIN_WAVES 6                          // waves per SIMD the register budget is cut for (A/B knob)
 #endif
-// (without the keys in the chunk the C2 kernel takes 71 VGPRs, 7 waves per SIMD, which 20.4 KB of LDS also allow.
+// (without the keys in the chunk the C2 kernel takes 72 VGPRs, 7 waves per SIMD, which 20.4 KB of LDS also allow.
 // Cut to 64 VGPRs with the staging buffer at 3968 matches, for 8 waves: C2 step equal within 1 %, all-candidate
 // batches 0.85 against 0.76 ms -- their tiles of ~4010 matches no longer fit the staging; and K >= 4 or a topic
 // column spill at 64.  profiles/stencil_sweep.md)
@@ -905,16 +995,13 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   __shared__ int32_t s_lastk[CARRY ? 2 : 1][CARRY ? 17 : 1];   // [tile & 1][m]: key of tile record 256m - 1 (m >= 1); [0][0]: before tile 0
   __shared__ int32_t s_firstk[CARRY ? 16 : 1];     // key of tile record 256m
   __shared__ int32_t s_wsum[2][ST_THREADS / 64];
-  __shared__ uint8_t s_tab[64];
-  __shared__ uint8_t s_lut[256];
-  __shared__ uint8_t s_nan[4];
+  __shared__ MaskTables<VT> s_mt;
   __shared__ int32_t s_out[CARRY ? 1 : ST_TILE];   // no carry: staged matches of the super-tile (see the tile loop's end)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
-  if (tid < 64) s_tab[tid] = P->table[tid];
-  s_lut[tid] = P->lut[tid];                       // (ST_THREADS == 256 entries)
-  if (tid < 4) s_nan[tid] = P->nan_mask[tid];
+  load_tables<VT>(s_mt, P, tid);
+  const MaskUni<VT> U = load_uni<VT>(P);
   const int64_t tile0 = int64_t(blockIdx.x) * SUB;
   const int ntl = int(ntiles - tile0 < SUB ? ntiles - tile0 : SUB);
 
@@ -939,7 +1026,7 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
   __syncthreads();                                // the tables
   uint32_t h_mask = 0;
   if (halo_lane && hg >= 0)
-    h_mask = mask_of<VT, TOPIC>(P, s_tab, s_nan, h_val, h_top, s_lut) | (uint32_t(CARRY && hg > 0 && h_prev == h_key) << 7);
+    h_mask = mask_of<VT, TOPIC>(P, s_mt, U, h_val, h_top) | (uint32_t(CARRY && hg > 0 && h_prev == h_key) << 7);
   int32_t h_bk = h_key;                           // carry: the history records' keys
   bool twice = false;                             // carry: a key claimed twice in this batch
 
@@ -958,33 +1045,41 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
     if constexpr (CARRY)
       if (tid == ST_THREADS - 1 && base + ST_TILE < n) nk = key[base + ST_TILE];
     uint32_t packed[4];
-    masks_of_chunk<VT, TOPIC>(cur, P, s_tab, s_nan, packed, s_lut);
+    masks_of_chunk<VT, TOPIC>(cur, P, s_mt, U, packed);
+    // the tile's image.  Only the batch's last tile has records >= n to mask (`left`, the records from
+    // this vector to the batch end, 64-bit): every other tile takes the arm where left is a constant
+    // (carry: a tile that ends the batch takes the tail arm too, its last vector has left == 4)
+    auto image = [&](auto whole) {
 #pragma unroll
-    for (int q = 0; q < ST_EPT / 4; q++) {
-      const int local = q * (ST_THREADS * 4) + tid * 4;
-      uint32_t w = packed[q];
-      const int64_t left = n - (base + local);    // records >= n match nothing
-      if constexpr (CARRY) {
-        const v4i k = cur.k[q];
-        // the record before this lane's first: lane - 1's last (DPP wave_shr:1; lane 0: resolved by readers)
-        const int32_t kp = __builtin_amdgcn_update_dpp(INT32_MIN, k[3], 0x138, 0xF, 0xF, false);
-        const uint32_t same = uint32_t(lane > 0 && kp == k[0]) | (uint32_t(k[1] == k[0]) << 8) |
-                              (uint32_t(k[2] == k[1]) << 16) | (uint32_t(k[3] == k[2]) << 24);
-        w |= same << 7;
-        if (lane == 0) s_firstk[4 * q + wid] = k[0];
-        if (lane == 63) s_lastk[j & 1][4 * q + wid + 1] = k[3];
-        // the keys a visit may read (see above)
-        const int32_t kn = __builtin_amdgcn_update_dpp(INT32_MIN, k[0], 0x130, 0xF, 0xF, false);   // wave_shl:1
-        // c_e: record e differs from the one before, or lies past the batch end (unloaded key)
-        const bool c1 = k[1] != k[0] || left <= 1, c2 = k[2] != k[1] || left <= 2, c3 = k[3] != k[2] || left <= 3;
-        if (lane == 0 || kp != k[0] || c1) s_bk[16 + local] = k[0];
-        if (c1 || c2) s_bk[16 + local + 1] = k[1];
-        if (c2 || c3) s_bk[16 + local + 2] = k[2];
-        if (c3 || lane == 63 || kn != k[3] || left <= 4) s_bk[16 + local + 3] = k[3];
+      for (int q = 0; q < ST_EPT / 4; q++) {
+        const int local = q * (ST_THREADS * 4) + tid * 4;
+        uint32_t w = packed[q];
+        const int64_t left = decltype(whole)::value ? int64_t(8) : n - (base + local);    // records >= n match nothing
+        if constexpr (CARRY) {
+          const v4i k = cur.k[q];
+          // the record before this lane's first: lane - 1's last (DPP wave_shr:1; lane 0: resolved by readers)
+          const int32_t kp = __builtin_amdgcn_update_dpp(INT32_MIN, k[3], 0x138, 0xF, 0xF, false);
+          const uint32_t same = uint32_t(lane > 0 && kp == k[0]) | (uint32_t(k[1] == k[0]) << 8) |
+                                (uint32_t(k[2] == k[1]) << 16) | (uint32_t(k[3] == k[2]) << 24);
+          w |= same << 7;
+          if (lane == 0) s_firstk[4 * q + wid] = k[0];
+          if (lane == 63) s_lastk[j & 1][4 * q + wid + 1] = k[3];
+          // the keys a visit may read (see above)
+          const int32_t kn = __builtin_amdgcn_update_dpp(INT32_MIN, k[0], 0x130, 0xF, 0xF, false);   // wave_shl:1
+          // c_e: record e differs from the one before, or lies past the batch end (unloaded key)
+          const bool c1 = k[1] != k[0] || left <= 1, c2 = k[2] != k[1] || left <= 2, c3 = k[3] != k[2] || left <= 3;
+          if (lane == 0 || kp != k[0] || c1) s_bk[16 + local] = k[0];
+          if (c1 || c2) s_bk[16 + local + 1] = k[1];
+          if (c2 || c3) s_bk[16 + local + 2] = k[2];
+          if (c3 || lane == 63 || kn != k[3] || left <= 4) s_bk[16 + local + 3] = k[3];
+        }
+        if constexpr (!decltype(whole)::value)
+          if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
+        *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
       }
-      if (left < 4) w &= left <= 0 ? 0u : (0xFFFFFFFFu >> (8 * (4 - left)));
-      *reinterpret_cast<uint32_t*>(&s_mask[16 + local]) = w;
-    }
+    };
+    if (CARRY ? base + ST_TILE < n : base + ST_TILE <= n) image(std::true_type{});   // uniform
+    else image(std::false_type{});
     if (tid < 16) s_mask[tid] = halo_lane ? uint8_t(h_mask) : 0;
     if constexpr (CARRY)
       if (tid < 16) s_bk[tid] = h_bk;
@@ -1012,19 +1107,22 @@ __global__ __launch_bounds__(ST_THREADS, CARRY ? ST_CARRY_WAVES : ST_PLAIN_WAVES
         S = (S & ~(1u << pb)) | (uint32_t(kb == s_firstk[m]) << pb);
       }
     }
-    uint32_t h = 0xFFFFFFFFu;
-    uint32_t Bs[K];
+    uint32_t h = 0xFFFFFFFFu;                     // bit p: the stages hold on window records p-K+1..p
+    uint32_t Bs[CARRY ? K : 1];                   // carry: stage s of every window record, for the boundary candidates
+    if constexpr (CARRY) {
 #pragma unroll
-    for (int s = 0; s < K; s++) {
-      uint32_t B = 0;
+      for (int s = 0; s < K; s++) {
+        uint32_t B = 0;
 #pragma unroll
-      for (int q = 0; q < 3; q++) B |= byte_bits(m8[q], s) << (8 * q);
-      Bs[s] = B;
-      h &= B << (K - 1 - s);
+        for (int q = 0; q < 3; q++) B |= byte_bits(m8[q], s) << (8 * q);
+        Bs[s] = B;
+        h &= B << (K - 1 - s);
+      }
+    } else {
+      // without carry: h holds the candidates (own records: bits 8..23); their keys decide
+      h = window_hits<K>(m8) << 8;
+      if constexpr (K > 1) S = window_same_keys<K>(key, base + ST_EPT * tid, n, h >> 8, key_mode, lane);
     }
-    // without carry: h holds the candidates (own records: bits 8..23); their keys decide
-    if constexpr (!CARRY && K > 1)
-      S = window_same_keys<K>(key, base + ST_EPT * tid, n, (h >> 8) & 0xFFFFu, key_mode, lane);
 #pragma unroll
     for (int d = 0; d < K - 1; d++) h &= S << d;
     uint32_t hit = (h >> 8) & 0xFFFFu;
