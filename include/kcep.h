@@ -63,7 +63,8 @@ extern "C" {
                                      kernel with deterministic per-start runs (variable-length matches) */
 #define CEP_PATH_FOLLOW 5         /* strict and skip-till-next (followedBy) stages of cardinality ONE / times(n):
                                      one deterministic walk per start record over per-slot bitmaps
-                                     (CEP_SESSION_FOLLOW, cep_pattern_follow); sessions without carry */
+                                     (CEP_SESSION_FOLLOW, cep_pattern_follow); sessions without carry, and
+                                     with CEP_SESSION_FOLLOW_CARRY carry sessions (waiting walks carried per key) */
 
 typedef struct cep_pattern cep_pattern;
 typedef struct cep_session cep_session;
@@ -202,6 +203,27 @@ typedef struct {
                                     for the match count.  The flag does nothing for a pattern that is not
                                     eligible, so a host may set it unconditionally.  Without the flag every
                                     pattern opens on the path it always did. */
+
+#define CEP_SESSION_FOLLOW_CARRY 128 /* opt-in: the follow path on CEP_SESSION_CARRY sessions too.  Implies
+                                    CEP_SESSION_FOLLOW; without CEP_SESSION_CARRY it is that flag.  A carry
+                                    session of a follow eligible pattern opens on CEP_PATH_FOLLOW (same automatic
+                                    order), and force_path = CEP_PATH_FOLLOW with carry succeeds only with this
+                                    flag.  The session carries, per key, every walk that waits for a later
+                                    record: k int64 words each -- the slots taken s (1 <= s <= k - 1), the stream
+                                    positions of those s records, zeros -- a key's walks in ascending start.
+                                    Batches follow the runs carry rules: taken without valid and with
+                                    CEP_BATCH_OFFSETS_MONOTONE, or with CEP_BATCH_FILTER; anything else fails
+                                    with CEP_E_UNSUPPORTED.  CEP_BATCH_ARRIVAL_ORDER works, CEP_BATCH_DELIVER is
+                                    accepted and does nothing more, CEP_BATCH_STOP_AT_ERROR is refused.  A batch
+                                    may complete more walks than it has records (2^31 or more:
+                                    CEP_E_RUN_CAPACITY).  Matches come as the runs path's CSR, stream positions,
+                                    by (completing record, start); cep_matches.path = CEP_PATH_FOLLOW.  A push
+                                    that fails its key checks leaves the walks and the marks untouched.
+                                    cep_state_* work as on a runs carry session with "KCSW" blobs (KCSR / KCST
+                                    blobs are refused with CEP_E_ARG); cep_state_positions of one returns every
+                                    walk's s positions; cep_key_state fails with CEP_E_UNSUPPORTED.  Not
+                                    composed with CEP_SESSION_MASK_PASS.  The flag does nothing for a pattern
+                                    that is not eligible. */
 
 #define CEP_MEM_HOST 0
 #define CEP_MEM_DEVICE 1

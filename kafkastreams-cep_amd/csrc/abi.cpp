@@ -12,7 +12,8 @@
 // Device paths:
 //   stencil  (stencil.hip)  strict single-cardinality patterns, SURVEY Q9
 //   runs     (runs.hip)     deterministic strict runs
-//   follow   (follow.hip)   strict and skip-till-next stages: one deterministic walk per start (opt-in)
+//   follow   (follow.hip)   strict and skip-till-next stages: one deterministic walk per start (opt-in;
+//                           carry sessions carry the waiting walks per key)
 //   general  (nfa.hip)      every pattern the IR expresses: one lane (or wave) per key
 //                           running the reference NFA over an HBM arena
 #include <dlfcn.h>
@@ -152,12 +153,14 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   const StencilProgram* sp = P.stencil_ok ? &P.stencil : masked ? &P.mask_stencil : nullptr;
   const int fast = sp && sp->chain ? CEP_PATH_CHAIN : CEP_PATH_STENCIL;   // the streaming kernel's flavour
   const bool carry = opts->flags & CEP_SESSION_CARRY;
-  // CEP_SESSION_FOLLOW: an eligible pattern's skip-till-next walks, on sessions without carry
-  const bool follow_flag = (opts->flags & CEP_SESSION_FOLLOW) && !carry && P.follow_ok;
+  // CEP_SESSION_FOLLOW: an eligible pattern's skip-till-next walks, on sessions without carry;
+  // CEP_SESSION_FOLLOW_CARRY: on carry sessions too (the waiting walks carried per key), and implies the former
+  const bool follow_carry = (opts->flags & CEP_SESSION_FOLLOW_CARRY) != 0;
+  const bool follow_flag = (((opts->flags & CEP_SESSION_FOLLOW) && !carry) || follow_carry) && P.follow_ok;
   if (path == 0) path = sp ? fast : follow_flag ? CEP_PATH_FOLLOW : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
   if (path == CEP_PATH_FOLLOW && !P.follow_ok)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: " + P.follow_why);
-  if (path == CEP_PATH_FOLLOW && carry)
+  if (path == CEP_PATH_FOLLOW && carry && !follow_carry)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: it takes sessions without CEP_SESSION_CARRY");
   if (path == CEP_PATH_RUNS && !P.runs_ok) return fail(CEP_E_UNSUPPORTED, "runs path does not apply: " + P.runs_why);
   if ((path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN) && !sp)
@@ -196,9 +199,11 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
     const StencilProgram& FP = P.follow;
     const size_t nt = size_t(follow_tiles(cap)), planes = size_t(FP.k) + 1;
     if (s->prog.ensure(sizeof(StencilProgram)) || s->total.ensure(64) || s->sum.ensure(64) ||
-        s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap)) || s->fw_bits.ensure(planes * nt * 64 * 8) ||
+        (!carry && s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap))) || s->fw_bits.ensure(planes * nt * 64 * 8) ||
         s->fw_sum.ensure(planes * nt * 8) || s->fw_tile.ensure(nt * 8) || s->fw_cnt.ensure(nt * 64 * 8) ||
-        s->fw_pre.ensure(nt * 64 * 8) || s->scan_tmp.ensure((nt / 16 + 4) * 8))
+        s->fw_pre.ensure(nt * 64 * 8) || s->scan_tmp.ensure((nt / 16 + 4) * 8) ||
+        // (a carry session writes the runs path's CSR instead of rows, and keeps the open starts apart)
+        (carry && (s->fw_open.ensure(nt * 64 * 8) || s->fw_ocnt.ensure(nt * 64 * 8) || s->fw_opre.ensure(nt * 64 * 8))))
       return cleanup(fail(CEP_E_HIP, "device allocation failed"));
     s->out_cap = cap;
     if (hipMemcpy(s->prog.p, &FP, sizeof(StencilProgram), hipMemcpyHostToDevice) || hipMemset(s->total.p, 0, s->total.cap))
@@ -240,7 +245,8 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
         s->hpos.ensure(size_t(opts->max_keys) * 2 * size_t(std::max(1, sp->k - 1)) * 8) ||
         hipMemset(s->halo.p, 0, size_t(opts->max_keys) * sizeof(HaloHdr)) || hipMemset(s->hflags.p, 0, 16))
       return cleanup(fail(CEP_E_HIP, "device allocation failed"));
-  } else if (carry && path == CEP_PATH_RUNS) {    // per key a carried tail, none yet (runs.hip)
+  } else if (carry && (path == CEP_PATH_RUNS || follow)) {   // per key a carried tail (runs.hip) / its waiting walks
+                                                             // (follow.hip), none yet
     s->carry = true;
     if (s->rtab.ensure(size_t(opts->max_keys) * 16) || s->rtop.ensure(8) || s->kstamp.ensure(size_t(opts->max_keys) * 4) ||
         hipMemset(s->rtab.p, 0, size_t(opts->max_keys) * 16) || hipMemset(s->rtop.p, 0, 8) ||
@@ -458,12 +464,12 @@ int cep_push_batch(cep_session* s, const cep_batch* b, void* stream) {
       if (filter_commit_launch(s->f_args, b->n, st) != hipSuccess) rc = fail(CEP_E_HIP, "filter_commit launch failed");
       s->base = base0 + b->n;
     }
-    if (!rc && arrival && s->last_path == CEP_PATH_RUNS) rc = arrival_csr(s, base0, b->n, st);
+    if (!rc && arrival && csr_batch(s)) rc = arrival_csr(s, base0, b->n, st);
     s->cur_pos = nullptr;
   } else if (arrival) {
     rc = group_batch(s, b, st, gb, gcols);
     if (!rc) rc = push_dispatch(s, &gb, st, stencil_batch);
-    if (!rc && (s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS)) rc = arrival_csr(s, base0, b->n, st);
+    if (!rc && csr_batch(s)) rc = arrival_csr(s, base0, b->n, st);
     s->cur_pos = nullptr;
   } else {
     rc = push_dispatch(s, b, st, stencil_batch);
@@ -499,6 +505,9 @@ static int push_dispatch(cep_session* s, const cep_batch* b, hipStream_t st, boo
   if (s->carry && s->path == CEP_PATH_RUNS)      // nor the runs path's carried tails
     return fail(CEP_E_UNSUPPORTED, "a runs carry session takes batches without null records (valid) and with "
                                    "per-key increasing offsets (CEP_BATCH_OFFSETS_MONOTONE)");
+  if (s->carry && s->path == CEP_PATH_FOLLOW)    // nor the follow path's carried walks
+    return fail(CEP_E_UNSUPPORTED, "a follow carry session takes batches without null records (valid) and with "
+                                   "per-key increasing offsets (CEP_BATCH_OFFSETS_MONOTONE)");
   if (!P.general_ok)
     return fail(CEP_E_UNSUPPORTED, "batch needs the general NFA path, which this pattern cannot use: " + P.general_why);
   s->last_path = CEP_PATH_GENERAL;
@@ -507,9 +516,8 @@ static int push_dispatch(cep_session* s, const cep_batch* b, hipStream_t st, boo
 
 const int64_t* cep_device_match_count(const cep_session* s) {
   if (!s) return nullptr;
-  // general and runs batches keep the count where their compaction scan left it
-  return s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS ? s->scal.as<int64_t>() + 3
-                                                                            : s->total.as<int64_t>();
+  // general, runs and follow carry batches keep the count where their compaction scan left it
+  return csr_batch(s) ? s->scal.as<int64_t>() + 3 : s->total.as<int64_t>();
 }
 
 int cep_match_count_to(const cep_session* s, int64_t* dst, void* stream) {
@@ -648,7 +656,7 @@ int cep_collect(cep_session* s, cep_matches* o) {
     return CEP_OK;
   }
   HIPCHECK(hipSetDevice(s->device));
-  if (s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS) {
+  if (csr_batch(s)) {
     HIPCHECK(hipStreamSynchronize(s->stream));
     const int64_t nm = s->g_matches, ne = s->g_entries;
     s->match_record.resize(size_t(nm));
@@ -807,7 +815,7 @@ int cep_collect_batch(cep_session* s, int64_t id, cep_matches* o) {
 int cep_checksum(cep_session* s, uint64_t* sum, int64_t* n_matches) {
   if (!s || !sum) return fail(CEP_E_ARG, "null argument");
   HIPCHECK(hipSetDevice(s->device));
-  if (s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS) {
+  if (csr_batch(s)) {
     cep_matches m;
     int rc = cep_collect(s, &m);
     if (rc) return rc;

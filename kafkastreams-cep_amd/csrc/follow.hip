@@ -40,7 +40,11 @@ struct FollowMaps {
   int64_t n;
   int32_t k;
   uint32_t next;                  // bit s: slot s is skip-till-next
+  const int64_t* pos;             // carry sessions: the records' stream positions (null: base + index)
+  int64_t base;
 };
+
+__device__ __forceinline__ int64_t pos_of(const FollowMaps& M, int64_t i) { return M.pos ? M.pos[i] : M.base + i; }
 
 // the first set bit of the plane at or after `from` and before `limit` (<= n); none: a value >= limit
 __device__ __forceinline__ int64_t next_set(const u64* __restrict__ plane, const u64* __restrict__ sum, int64_t from,
@@ -61,11 +65,51 @@ __device__ __forceinline__ int64_t next_set(const u64* __restrict__ plane, const
   return w * 64 + __builtin_ctzll(plane[w]);       // (not zero: its second-level bit is set)
 }
 
-// the walk from start j0: its last record, or -1 if it dies or does not complete in the batch; row: its
+// A walk that does not complete either dies (a strict hop lands on a record of the key that does not
+// satisfy the slot) or stays open (a hop reaches the end of the key's segment: on a carry session it
+// goes on in the key's next batch); without carry both mean "no match".
+constexpr int64_t FW_DEAD = -1, FW_OPEN = -2;
+
+// a walk continued at slot s0 from record p (a strict slot tests p, a skip-till-next slot searches from
+// p) within the key segment ending at `end`: its last record, FW_DEAD, or FW_OPEN with *reached = the
+// slots taken.  row: the records taken, by slot (or null); prow: their stream positions, slot s at
+// prow[s * pstride] (or null)
+__device__ __forceinline__ int64_t follow_steps(const FollowMaps& M, int64_t p, int s0, int64_t end,
+                                                int32_t* __restrict__ row, int64_t* __restrict__ prow, int pstride,
+                                                int* reached) {
+  int64_t last = p - 1;
+  for (int s = s0; s < M.k; s++) {
+    const u64* plane = M.bits + s * M.wpl;
+    const bool next = M.next >> s & 1;
+    if (next) p = next_set(plane, M.sum + s * M.nt, p, end);
+    if (p >= end) {
+      if (reached) *reached = s;
+      return FW_OPEN;
+    }
+    if (!next && !(plane[p >> 6] >> (p & 63) & 1)) return FW_DEAD;
+    if (row) row[s] = int32_t(p);
+    if (prow) prow[s * pstride] = pos_of(M, p);
+    last = p++;
+  }
+  return last;
+}
+
+// the end of the key segment that holds record j
+__device__ __forceinline__ int64_t segment_end(const FollowMaps& M, int64_t j) {
+  const int64_t E = next_set(M.bits + M.k * M.wpl, M.sum + M.k * M.nt, j + 1, M.n);
+  return E < M.n ? E : M.n;
+}
+
+// the walk from start j0: its last record, or FW_DEAD / FW_OPEN (both < 0)
+__device__ __forceinline__ int64_t follow_walk_open(const FollowMaps& M, int64_t j0) {
+  return follow_steps(M, j0 + 1, 1, segment_end(M, j0), nullptr, nullptr, 0, nullptr);
+}
+
+// ... as the sessions without carry walk it, where dead and open are both "no match" (-1): the loop those
+// kernels have always run, kept apart from follow_steps so that their code does not move with it; row: its
 // records, slot by slot (or null)
 __device__ __forceinline__ int64_t follow_walk(const FollowMaps& M, int64_t j0, int32_t* __restrict__ row) {
-  const int64_t E = next_set(M.bits + M.k * M.wpl, M.sum + M.k * M.nt, j0 + 1, M.n);   // the key segment's end
-  const int64_t end = E < M.n ? E : M.n;
+  const int64_t end = segment_end(M, j0);
   int64_t p = j0;
   if (row) row[0] = int32_t(j0);
   for (int s = 1; s < M.k; s++) {
@@ -177,14 +221,23 @@ __global__ __launch_bounds__(ST_THREADS) void follow_bits(const int32_t* __restr
 }
 
 // ---- follow_count / follow_write: a workgroup per tile, each wave 16 words of slot 0's bitmap ----
-template <bool WRITE>
+// CARRY (count pass of a carry session): also the starts whose walk is open at the batch end, as a bitmap
+// plane (open) and per word a count (wopen)
+template <bool WRITE, bool CARRY>
 __global__ __launch_bounds__(256) void follow_walks(FollowMaps M, const int64_t* __restrict__ tile_starts,
                                                    int64_t* __restrict__ wcnt, const int64_t* __restrict__ wpre,
-                                                   u64* __restrict__ keys, u64* __restrict__ max_span) {
+                                                   u64* __restrict__ keys, u64* __restrict__ max_span,
+                                                   u64* __restrict__ open, int64_t* __restrict__ wopen) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t tile = blockIdx.x;
   if (tile_starts[tile] == 0) {                    // uniform
-    if (!WRITE && threadIdx.x < 64) wcnt[tile * 64 + threadIdx.x] = 0;
+    if (!WRITE && threadIdx.x < 64) {
+      wcnt[tile * 64 + threadIdx.x] = 0;
+      if (CARRY) {
+        wopen[tile * 64 + threadIdx.x] = 0;
+        open[tile * 64 + threadIdx.x] = 0;
+      }
+    }
     return;
   }
   int64_t span = 0;
@@ -193,18 +246,31 @@ __global__ __launch_bounds__(256) void follow_walks(FollowMaps M, const int64_t*
     if (WRITE && wcnt[w] == 0) continue;           // uniform per wave
     const u64 x = M.bits[w];
     if (x == 0) {
-      if (!WRITE && lane == 0) wcnt[w] = 0;
+      if (!WRITE && lane == 0) {
+        wcnt[w] = 0;
+        if (CARRY) {
+          wopen[w] = 0;
+          open[w] = 0;
+        }
+      }
       continue;
     }
     const int64_t j0 = w * 64 + lane;
-    int64_t e = -1;
-    if (x >> lane & 1) e = follow_walk(M, j0, nullptr);
+    int64_t e = FW_DEAD;
+    if (x >> lane & 1) e = CARRY ? follow_walk_open(M, j0) : follow_walk(M, j0, nullptr);
     const u64 done = __ballot(e >= 0);
     if (WRITE) {
       if (e >= 0) keys[wpre[w] + __popcll(done & ((1ull << lane) - 1))] = (u64(e) << 31) | u64(j0);
     } else {
       if (lane == 0) wcnt[w] = __popcll(done);
       if (e >= 0 && e - j0 > span) span = e - j0;
+      if (CARRY) {
+        const u64 op = __ballot(e == FW_OPEN);
+        if (lane == 0) {
+          open[w] = op;
+          wopen[w] = __popcll(op);
+        }
+      }
     }
   }
   if (!WRITE) {
@@ -229,7 +295,7 @@ __global__ __launch_bounds__(256) void follow_rows(FollowMaps M, const u64* __re
 
 static FollowMaps follow_maps(const FollowArgs& A) {
   const int64_t nt = follow_tiles(A.n);
-  return FollowMaps{A.bits, A.sum, nt * 64, nt, A.n, A.k, A.next_mask};
+  return FollowMaps{A.bits, A.sum, nt * 64, nt, A.n, A.k, A.next_mask, A.pos, A.base};
 }
 
 template <class VT>
@@ -261,21 +327,241 @@ hipError_t follow_count_launch(const FollowArgs& A, hipStream_t st) {
   const int64_t nt = follow_tiles(A.n);
   hipError_t e = hipMemsetAsync(A.max_span, 0, 8, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(follow_walks<false>, dim3(unsigned(nt)), dim3(256), 0, st, follow_maps(A), A.tile_starts, A.wcnt,
-                     A.wpre, A.keys, A.max_span);
+  hipLaunchKernelGGL((follow_walks<false, false>), dim3(unsigned(nt)), dim3(256), 0, st, follow_maps(A), A.tile_starts,
+                     A.wcnt, A.wpre, A.keys, A.max_span, nullptr, nullptr);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return exclusive_scan(A.wcnt, nt * 64, A.wpre, A.nm, A.scan_tmp, st);
 }
 
 hipError_t follow_write_launch(const FollowArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(follow_walks<true>, dim3(unsigned(follow_tiles(A.n))), dim3(256), 0, st, follow_maps(A),
-                     A.tile_starts, A.wcnt, A.wpre, A.keys, A.max_span);
+  hipLaunchKernelGGL((follow_walks<true, false>), dim3(unsigned(follow_tiles(A.n))), dim3(256), 0, st, follow_maps(A),
+                     A.tile_starts, A.wcnt, A.wpre, A.keys, A.max_span, nullptr, nullptr);
   return hipGetLastError();
 }
 
 hipError_t follow_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int32_t* out,
                               int64_t* total, hipStream_t st) {
   hipLaunchKernelGGL(follow_rows, dim3(blocks256(nm)), dim3(256), 0, st, follow_maps(A), sorted, nm, out, total);
+  return hipGetLastError();
+}
+
+// ---- carry sessions (CEP_SESSION_FOLLOW_CARRY): carried walks ----
+// A walk open at the end of a batch waits for its key's next records: it is carried as k int64 words (slots
+// taken s, the stream positions of its s records, zeros), a key's walks contiguous in ascending start
+// (launch.h FollowCarry).  Every waiting walk of a key at slot s takes the same records of the key's next
+// segment, so a batch continues its keys' walks once per (segment, slot) -- follow_resume, k - 1 lanes per
+// segment however many walks wait -- and each carried walk is a table lookup and a copy.  Matches come out
+// by (completing record, start): carried walks start before every in-batch start of their key and equal
+// completing records imply one key, so the sort input is the completed carried walks in (segment, list)
+// order, marked above the sorted bits, then the in-batch ones in start order, and the sort is stable.
+// A key's new list: its surviving carried walks in order, then its open in-batch walks in start order,
+// appended at *rtop; placement is ordered (prefixes and ranks), no atomics.
+namespace {
+
+constexpr int32_t FR_DEAD = 0, FR_DONE = 1, FR_OPEN = 2;   // a continuation's outcome (open: | slots reached << 8)
+constexpr u64 FC_MARK = 1ull << 63;                        // a sort key of a carried walk: its low bits number it
+
+// the in-batch starts with an open walk before record j
+struct OpenRank {
+  const u64* open;
+  const int64_t* wopre;
+  const int64_t* nopen;
+  int64_t n;
+};
+__device__ __forceinline__ int64_t open_rank(const OpenRank& R, int64_t j) {
+  if (j >= R.n) return *R.nopen;
+  return R.wopre[j >> 6] + __popcll(R.open[j >> 6] & ((1ull << (j & 63)) - 1));
+}
+// the carried walks that stay open among the first x of the enumeration
+__device__ __forceinline__ int64_t open_before(const FollowCarry& C, int64_t x) {
+  return x < *C.ncw && x < C.bound ? C.cw_opre[x] : *C.nco;
+}
+// the segment of the enumeration's x-th carried walk: the last whose walks start at or before x
+__device__ __forceinline__ int64_t walk_segment(const FollowCarry& C, int64_t x) {
+  int64_t lo = 0, hi = *C.nseg - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (C.toff[mid] <= x) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ const int64_t* walk_words(const FollowCarry& C, const int32_t* __restrict__ key, int k,
+                                                     int64_t sg, int64_t x, int32_t* kk) {
+  *kk = key[C.seg_start[sg]];
+  return C.rpool + (C.rtab[2 * int64_t(*kk)] + (x - C.toff[sg])) * k;
+}
+
+// one lane per (segment whose key has walks, slot 1..k-1): the walk continued from the segment's first record
+__global__ __launch_bounds__(256) void follow_resume(FollowMaps M, FollowCarry C, int64_t items) {
+  const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (t >= items) return;
+  const int km1 = M.k - 1;
+  const int64_t sg = t / km1;
+  const int s = 1 + int(t % km1);
+  if (sg >= *C.nseg || C.tlen[sg] == 0) return;
+  int32_t* row = C.res + t * M.k;
+  int reached = s;
+  const int64_t e = follow_steps(M, C.seg_start[sg], s, C.seg_start[sg + 1], row, nullptr, 0, &reached);
+  row[0] = e >= 0 ? FR_DONE : e == FW_OPEN ? (FR_OPEN | reached << 8) : FR_DEAD;
+}
+
+// per carried walk of the batch's keys: completed / still open (dead: neither)
+__global__ __launch_bounds__(256) void follow_classify(FollowCarry C, const int32_t* __restrict__ key, int k) {
+  const int64_t x = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (x >= C.bound || x >= *C.ncw) return;
+  const int64_t sg = walk_segment(C, x);
+  int32_t st = FR_DEAD;
+  if (sg < C.nseg_cap) {                           // (past it: a batch the key check rejects)
+    int32_t kk;
+    const int64_t s = walk_words(C, key, k, sg, x, &kk)[0];
+    if (s >= 1 && s < k) st = C.res[(sg * (k - 1) + s - 1) * k] & 3;
+  }
+  C.cw_done[x] = st == FR_DONE;
+  C.cw_open[x] = st == FR_OPEN;
+}
+
+// the completed carried walks' sort keys; the surviving ones, extended by the records taken, into the pool
+__global__ __launch_bounds__(256) void follow_carried_out(FollowMaps M, FollowCarry C, OpenRank R,
+                                                         const int32_t* __restrict__ key, u64* __restrict__ keys) {
+  const int64_t x = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (x >= C.bound || x >= *C.ncw) return;
+  const bool done = C.cw_done[x] != 0, open = C.cw_open[x] != 0;
+  if (!done && !open) return;
+  const int k = M.k;
+  const int64_t sg = walk_segment(C, x);
+  int32_t kk;
+  const int64_t* src = walk_words(C, key, k, sg, x, &kk);
+  const int s = int(src[0]);
+  const int32_t* row = C.res + (sg * (k - 1) + s - 1) * k;
+  if (done) {
+    const int64_t c = C.cw_dpre[x];
+    keys[c] = FC_MARK | (u64(uint32_t(row[k - 1])) << 31) | u64(c);
+    C.cd_x[c] = x;
+    return;
+  }
+  const int reached = row[0] >> 8;
+  int64_t* d = C.rpool + (*C.rtop + C.cw_opre[x] + open_rank(R, C.seg_start[sg])) * k;
+  d[0] = reached;
+  for (int t = 1; t < k; t++) d[t] = t <= s ? src[t] : t <= reached ? pos_of(M, row[t - 1]) : 0;
+}
+
+// the CSR of the ordered matches: entries final slot first, stream positions
+__global__ __launch_bounds__(256) void follow_carry_rows(FollowMaps M, FollowCarry C, const int32_t* __restrict__ key,
+                                                        const StencilProgram* __restrict__ P,
+                                                        const u64* __restrict__ sorted, int64_t nm,
+                                                        int64_t* __restrict__ match_record, int32_t* __restrict__ match_key,
+                                                        int64_t* __restrict__ ent_off, int32_t* __restrict__ ent_name,
+                                                        int64_t* __restrict__ ent_record, int64_t* __restrict__ total) {
+  const int64_t m = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (m == 0) *total = nm;
+  if (m >= nm) return;
+  const int k = M.k;
+  const u64 v = sorted[m];
+  int64_t* er = ent_record + m * k;
+  if (v & FC_MARK) {
+    // a carried walk: its prefix from the pool, the rest from its continuation -- every load before the
+    // row's stores (DESIGN 4.1 "the gather's loads")
+    const int64_t x = C.cd_x[v & 0x7FFFFFFFull];
+    const int64_t sg = walk_segment(C, x);
+    int32_t kk;
+    const int64_t* src = walk_words(C, key, k, sg, x, &kk);
+    const int s = int(src[0]);
+    const int32_t* row = C.res + (sg * (k - 1) + s - 1) * k;
+    int64_t pv[STENCIL_MAX_K], last = 0;
+#pragma unroll
+    for (int t = 0; t < STENCIL_MAX_K; t++) {
+      pv[t] = 0;
+      if (t < k) pv[t] = t < s ? src[1 + t] : pos_of(M, row[t]);
+      if (t == k - 1) last = pv[t];
+    }
+#pragma unroll
+    for (int t = 0; t < STENCIL_MAX_K; t++)
+      if (t < k) er[k - 1 - t] = pv[t];
+    match_record[m] = last;
+    match_key[m] = kk;
+  } else {
+    const int64_t j0 = int64_t(v & 0x7FFFFFFFull);
+    er[k - 1] = pos_of(M, j0);
+    const int64_t e = follow_steps(M, j0 + 1, 1, segment_end(M, j0), nullptr, er + k - 1, -1, nullptr);
+    match_record[m] = pos_of(M, e);
+    match_key[m] = key[j0];
+  }
+  ent_off[m] = m * k;
+  for (int t = 0; t < k; t++) ent_name[m * k + k - 1 - t] = P->name[t];
+}
+
+// the open in-batch walks behind their key's surviving carried ones, in start order
+__global__ __launch_bounds__(256) void follow_open_write(FollowMaps M, FollowCarry C, OpenRank R) {
+  const int64_t j0 = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (j0 >= M.n || !(R.open[j0 >> 6] >> (j0 & 63) & 1)) return;
+  const int k = M.k;
+  const int64_t sg = C.seg_idx[j0] + C.seg_flag[j0] - 1;
+  int64_t* d = C.rpool + (*C.rtop + open_before(C, C.toff[sg + 1]) + open_rank(R, j0)) * k;
+  int reached = 1;
+  d[1] = pos_of(M, j0);
+  (void)follow_steps(M, j0 + 1, 1, segment_end(M, j0), nullptr, d + 1, 1, &reached);
+  d[0] = reached;
+  for (int t = reached + 1; t < k; t++) d[t] = 0;
+}
+
+// the table entries of the batch's keys (a key absent from the batch keeps its own)
+__global__ __launch_bounds__(256) void follow_tab(FollowCarry C, OpenRank R, const int32_t* __restrict__ key, int64_t nmax) {
+  const int64_t sg = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (sg >= nmax || sg >= *C.nseg) return;
+  const int64_t kk = key[C.seg_start[sg]];
+  const int64_t o0 = open_before(C, C.toff[sg]), o1 = open_before(C, C.toff[sg + 1]);
+  const int64_t r0 = open_rank(R, C.seg_start[sg]), r1 = open_rank(R, C.seg_start[sg + 1]);
+  const int64_t cnt = (o1 - o0) + (r1 - r0);
+  if (cnt) C.rtab[2 * kk] = *C.rtop + o0 + r0;
+  C.rtab[2 * kk + 1] = cnt;
+}
+__global__ void follow_top_add(int64_t* __restrict__ top, const int64_t* __restrict__ a, const int64_t* __restrict__ b) {
+  *top += *a + *b;
+}
+
+OpenRank open_rank_args(const FollowArgs& A) { return OpenRank{A.open, A.wopre, A.nopen, A.n}; }
+
+}  // namespace
+
+hipError_t follow_carry_count_launch(const FollowArgs& A, const FollowCarry& C, hipStream_t st) {
+  const int64_t nt = follow_tiles(A.n);
+  hipError_t e = hipMemsetAsync(A.max_span, 0, 8, st);
+  if (e != hipSuccess) return e;
+  if (C.bound > 0) {
+    const int64_t items = C.nseg_cap * (A.k - 1);
+    hipLaunchKernelGGL(follow_resume, dim3(blocks256(items)), dim3(256), 0, st, follow_maps(A), C, items);
+    hipLaunchKernelGGL(follow_classify, dim3(blocks256(C.bound)), dim3(256), 0, st, C, A.key, A.k);
+    if ((e = exclusive_scan_pair(C.cw_done, C.cw_open, C.bound, C.ncw, C.cw_dpre, C.cw_opre, C.ncd, C.nco, C.scan_tmp,
+                                 st)) != hipSuccess)
+      return e;
+  }
+  hipLaunchKernelGGL((follow_walks<false, true>), dim3(unsigned(nt)), dim3(256), 0, st, follow_maps(A), A.tile_starts,
+                     A.wcnt, A.wpre, A.keys, A.max_span, A.open, A.wopen);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return exclusive_scan_pair(A.wcnt, A.wopen, nt * 64, nullptr, A.wpre, A.wopre, A.nm, A.nopen, C.scan_tmp, st);
+}
+
+hipError_t follow_carry_keys_launch(const FollowArgs& A, const FollowCarry& C, int64_t ncd, hipStream_t st) {
+  if (C.bound > 0)
+    hipLaunchKernelGGL(follow_carried_out, dim3(blocks256(C.bound)), dim3(256), 0, st, follow_maps(A), C,
+                       open_rank_args(A), A.key, A.keys);
+  hipLaunchKernelGGL((follow_walks<true, false>), dim3(unsigned(follow_tiles(A.n))), dim3(256), 0, st, follow_maps(A),
+                     A.tile_starts, A.wcnt, A.wpre, A.keys + ncd, A.max_span, nullptr, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t follow_carry_rows_launch(const FollowArgs& A, const FollowCarry& C, const unsigned long long* sorted,
+                                    int64_t nm, int64_t* match_record, int32_t* match_key, int64_t* ent_off,
+                                    int32_t* ent_name, int64_t* ent_record, int64_t* total, hipStream_t st) {
+  hipLaunchKernelGGL(follow_carry_rows, dim3(blocks256(nm)), dim3(256), 0, st, follow_maps(A), C, A.key, A.prog_dev,
+                     sorted, nm, match_record, match_key, ent_off, ent_name, ent_record, total);
+  return hipGetLastError();
+}
+
+hipError_t follow_carry_state_launch(const FollowArgs& A, const FollowCarry& C, hipStream_t st) {
+  hipLaunchKernelGGL(follow_open_write, dim3(blocks256(A.n)), dim3(256), 0, st, follow_maps(A), C, open_rank_args(A));
+  hipLaunchKernelGGL(follow_tab, dim3(blocks256(A.n)), dim3(256), 0, st, C, open_rank_args(A), A.key, A.n);
+  hipLaunchKernelGGL(follow_top_add, dim3(1), dim3(1), 0, st, C.rtop, C.nco, A.nopen);
   return hipGetLastError();
 }
 

@@ -210,7 +210,52 @@ struct FollowArgs {
   int64_t* nm;                      // device: completed walks
   unsigned long long* max_span;     // device: the longest last record - start
   unsigned long long* keys;         // the completed walks in start order, (last record << 31) | start
+  // carry sessions (CEP_SESSION_FOLLOW_CARRY): the records' stream positions (pos, or null: base + index), the
+  // plane of the starts whose walk is open at the batch end (64 t words), their count per word and its prefix
+  const int64_t* pos;
+  int64_t base;
+  unsigned long long* open;
+  int64_t* wopen;
+  int64_t* wopre;
+  int64_t* nopen;                   // device: open in-batch walks
 };
+// The carried walks of a follow carry session (follow.hip): a walk is k int64 words -- slots taken s, the
+// stream positions of its s records, zeros -- in the runs path's tail pool (rtab: offset and count per key,
+// records of k words).  The batch's segments (nfa_segments), per segment its key's walks (tlen, prefix toff,
+// n + 1 entries each), their number *ncw <= bound (the host's: every walk the pool holds).
+struct FollowCarry {
+  const int64_t* nseg;
+  const int64_t* seg_start;
+  const int64_t* seg_flag;
+  const int64_t* seg_idx;
+  int64_t nseg_cap;                 // segments the continuation table holds (min(n, max_keys): a valid batch's bound)
+  const int64_t* tlen;
+  const int64_t* toff;
+  const int64_t* ncw;
+  int64_t bound;
+  int64_t* rtab;
+  int64_t* rpool;
+  int64_t* rtop;
+  int32_t* res;                     // per (segment, slot 1..k-1) k ints: the continuation (follow_resume)
+  int64_t *cw_done, *cw_open;       // per carried walk of the batch's keys: completed / still open (bound entries)
+  int64_t *cw_dpre, *cw_opre;       // their exclusive prefixes
+  int64_t *ncd, *nco;               // device: their totals
+  int64_t* cd_x;                    // per completed carried walk: its number in the enumeration
+  int64_t* scan_tmp;                // 2 x (max(64 t, bound) / 1024 + 1) words
+};
+// the counts of a carry batch before its one host synchronisation: the continuations, the carried walks
+// classified and scanned, the in-batch walks counted (completed: A.nm, open: A.nopen) and scanned
+hipError_t follow_carry_count_launch(const FollowArgs& A, const FollowCarry& C, hipStream_t st);
+// the sort input (A.keys): the ncd completed carried walks, then the in-batch ones; the surviving carried
+// walks appended to the pool at *rtop (room reserved by the caller)
+hipError_t follow_carry_keys_launch(const FollowArgs& A, const FollowCarry& C, int64_t ncd, hipStream_t st);
+// the CSR of the nm ordered matches; *total = nm
+hipError_t follow_carry_rows_launch(const FollowArgs& A, const FollowCarry& C, const unsigned long long* sorted,
+                                    int64_t nm, int64_t* match_record, int32_t* match_key, int64_t* ent_off,
+                                    int32_t* ent_name, int64_t* ent_record, int64_t* total, hipStream_t st);
+// the open in-batch walks appended behind their keys' surviving carried ones, the batch's keys' table
+// entries, *rtop advanced
+hipError_t follow_carry_state_launch(const FollowArgs& A, const FollowCarry& C, hipStream_t st);
 int64_t follow_tiles(int64_t n);
 hipError_t follow_bits_launch(const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
 hipError_t follow_count_launch(const FollowArgs& A, hipStream_t st);

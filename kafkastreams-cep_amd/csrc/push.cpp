@@ -584,6 +584,114 @@ int push_runs(cep_session* s, const cep_batch* b, hipStream_t st) {
   return CEP_OK;
 }
 
+// A follow carry session's batch (CEP_SESSION_FOLLOW_CARRY, follow.hip "carried walks"): the batch is read in
+// place; its keys' waiting walks are continued once per (segment, slot), the in-batch walks counted with the
+// open ones kept apart; after the one host synchronisation the matches are ordered and written as the runs
+// path's CSR, and the keys' new walk lists appended to the pool.  Nothing of the session's state is written
+// before the key checks are read: a rejected push leaves it as it was.
+static int push_follow_carry(cep_session* s, FollowArgs& A, hipStream_t st) {
+  const int64_t n = A.n, nt = follow_tiles(n);
+  const int K = A.k;
+  const int64_t bound = s->rpool_used;            // every walk the pool holds: the carried kernels' launch bound
+  const int64_t nseg_cap = std::min<int64_t>(n, s->opts.max_keys);
+  int rc = CEP_OK;
+  if (s->flag.ensure(size_t(n) * 8) || s->idx.ensure(size_t(n) * 8) || s->seg.ensure(size_t(n + 1) * 8) ||
+      s->rc_a.ensure(size_t(n + 2) * 8) || s->rc_b.ensure(size_t(n + 2) * 8) || s->ctl.ensure(128) ||
+      s->scan_tmp.ensure(size_t(2 * (std::max({nt * 64, bound, n}) / 1024 + 2) + 4) * 8) ||
+      (bound > 0 && (s->fw_res.ensure(size_t(nseg_cap) * size_t(K - 1) * size_t(K) * 4) || s->fw_cdone.ensure(size_t(bound) * 8) ||
+                     s->fw_copen.ensure(size_t(bound) * 8) || s->fw_cdpre.ensure(size_t(bound) * 8) ||
+                     s->fw_copre.ensure(size_t(bound) * 8) || s->fw_cdx.ensure(size_t(bound) * 8))))
+    return fail(CEP_E_HIP, "allocation failed");
+  int64_t* scal = s->scal.as<int64_t>();
+  int64_t* ctl = s->ctl.as<int64_t>();            // in-batch completed, open; carried walks, completed, open; span
+  A.pos = s->cur_pos;
+  A.base = s->base;
+  A.scan_tmp = s->scan_tmp.as<int64_t>();
+  A.open = s->fw_open.as<unsigned long long>();
+  A.wopen = s->fw_ocnt.as<int64_t>();
+  A.wopre = s->fw_opre.as<int64_t>();
+  A.nm = ctl;
+  A.nopen = ctl + 1;
+  A.max_span = reinterpret_cast<unsigned long long*>(ctl + 5);
+  FollowCarry C{};
+  C.nseg = scal;
+  C.seg_start = s->seg.as<int64_t>();
+  C.seg_flag = s->flag.as<int64_t>();
+  C.seg_idx = s->idx.as<int64_t>();
+  C.nseg_cap = nseg_cap;
+  C.tlen = s->rc_a.as<int64_t>();
+  C.toff = s->rc_b.as<int64_t>();
+  C.ncw = ctl + 2;
+  C.bound = bound;
+  C.rtab = s->rtab.as<int64_t>();
+  C.rpool = s->rpool.as<int64_t>();
+  C.rtop = s->rtop.as<int64_t>();
+  C.res = s->fw_res.as<int32_t>();
+  C.cw_done = s->fw_cdone.as<int64_t>(); C.cw_open = s->fw_copen.as<int64_t>();
+  C.cw_dpre = s->fw_cdpre.as<int64_t>(); C.cw_opre = s->fw_copre.as<int64_t>();
+  C.ncd = ctl + 3; C.nco = ctl + 4;
+  C.cd_x = s->fw_cdx.as<int64_t>();
+  C.scan_tmp = s->scan_tmp.as<int64_t>();
+  HIPCHECK(set_words_launch(ctl, 6, 0, 0, st));
+  HIPCHECK(nfa_segments(A.key, n, s->flag.as<int64_t>(), s->idx.as<int64_t>(), s->seg.as<int64_t>(), scal,
+                        s->scan_tmp.as<int64_t>(), st));
+  HIPCHECK(hipMemsetAsync(scal + 1, 0, 8, st));
+  HIPCHECK(carry_keycheck_launch(n, scal, A.key, s->seg.as<int64_t>(), max_keys32(s), s->kstamp.as<int32_t>(),
+                                 ++s->batch_no, reinterpret_cast<unsigned long long*>(scal + 1), st));
+  RcIn B{};
+  B.key = A.key;
+  // per segment its key's waiting walks and their prefix (the runs path's tail lengths: the same table)
+  HIPCHECK(runs_carry_build(B, n, s->base, nullptr, nullptr, s->seg.as<int64_t>(), scal, s->rtab.as<int64_t>(),
+                            s->rpool.as<int64_t>(), s->rc_a.as<int64_t>(), s->rc_b.as<int64_t>(), ctl + 2,
+                            s->scan_tmp.as<int64_t>(), RcExt{}, st, true, max_keys32(s)));
+  HIPCHECK(follow_bits_launch(A, s->timing ? s->ev0.e : nullptr, s->timing ? s->ev1.e : nullptr, st));
+  HIPCHECK(follow_carry_count_launch(A, C, st));
+  // the batch's one host synchronisation: the completed and open walks, in-batch and carried, the longest
+  // in-batch span, the key-check flags
+  int64_t* h_res_dev = nullptr;
+  if ((rc = results_page(s, &h_res_dev))) return rc;
+  HIPCHECK(gather_words_launch(ctl, 6, scal, 2, h_res_dev, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  if ((rc = key_check(uint64_t(s->h_res[7])))) return rc;
+  const int64_t nm_in = s->h_res[0], nopen = s->h_res[1], ncd = s->h_res[3], nco = s->h_res[4], span = s->h_res[5];
+  const int64_t nm = nm_in + ncd;                 // (carried walks complete too: more matches than records, possibly)
+  if (nm_in < 0 || nm_in > n || ncd < 0 || ncd > bound || nm >= (int64_t(1) << 31))
+    return fail(CEP_E_RUN_CAPACITY, "a follow carry batch completes 2^31 walks or more");
+  if ((rc = tail_reserve(s, nopen + nco, st))) return rc;   // room for the keys' new lists (the pool may move)
+  C.rpool = s->rpool.as<int64_t>();
+  int bits = 1;                                    // bits of the completing record
+  while ((int64_t(1) << bits) <= n) bits++;
+  const bool ranked = ncd == 0 && span <= 1024 && !getenv_flag("KCEP_RUNS_RADIX");
+  size_t tmp_bytes = 0;
+  if (!ranked && nm > 0) HIPCHECK(runs_sort(nullptr, nullptr, nm, bits, nullptr, &tmp_bytes, st));
+  const size_t nmb = size_t(std::max<int64_t>(nm, 1)), neb = nmb * size_t(K);
+  if (s->rk.ensure(nmb * 8) || s->rk_sorted.ensure(nmb * 8) ||
+      (ranked ? s->r_len.ensure(nmb * 8) : s->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16))) ||
+      s->o_record.ensure(nmb * 8) || s->o_key.ensure(nmb * 4) || s->o_entoff.ensure(nmb * 8) || s->o_name.ensure(neb * 4) ||
+      s->o_entrec.ensure(neb * 8))
+    return fail(CEP_E_HIP, "allocation failed");
+  A.keys = s->rk.as<unsigned long long>();
+  HIPCHECK(follow_carry_keys_launch(A, C, ncd, st));
+  // (completing record, start) order: the stable sort over the completing record's bits keeps the carried
+  // walks in front of their key's in-batch ones; the windowed rank only where none completed
+  if (nm > 0) {
+    if (ranked)
+      HIPCHECK(runs_order_launch(A.keys, nm, int(span), s->rk_sorted.as<unsigned long long>(), s->r_len.as<int64_t>(), st));
+    else
+      HIPCHECK(runs_sort(A.keys, s->rk_sorted.as<unsigned long long>(), nm, bits, s->rk_tmp.p, &tmp_bytes, st));
+  }
+  HIPCHECK(follow_carry_rows_launch(A, C, s->rk_sorted.as<unsigned long long>(), nm, s->o_record.as<int64_t>(),
+                                    s->o_key.as<int32_t>(), s->o_entoff.as<int64_t>(), s->o_name.as<int32_t>(),
+                                    s->o_entrec.as<int64_t>(), scal + 3, st));
+  HIPCHECK(follow_carry_state_launch(A, C, st));
+  s->rpool_used += nopen + nco;
+  s->base += n;
+  s->g_matches = nm;
+  s->g_entries = nm * K;
+  if (s->timing) HIPCHECK(hipEventRecord(s->eb1, st));
+  return CEP_OK;
+}
+
 // Skip-till-next walks (follow.hip): the slots' bitmaps in one streaming pass, the completed walks counted
 // and compacted in start order, ordered by (completing record, start) as the runs path orders its runs, then
 // written as K-int rows -- from there the batch is a finished stencil batch without carry (cep_collect).
@@ -595,6 +703,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   int rc = stage_inputs(s, b, st, in, true);
   if (rc) return rc;
   s->d_key = in.key;
+  if (s->carry) reset_results(s);
   if (n == 0) {
     HIPCHECK(hipMemsetAsync(s->total.p, 0, 8, st));
     return push_empty(s, st, true);
@@ -625,6 +734,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   A.scan_tmp = s->scan_tmp.as<int64_t>();
   A.nm = scal + 4;
   A.max_span = reinterpret_cast<unsigned long long*>(scal + 5);
+  if (s->carry) return push_follow_carry(s, A, st);
   HIPCHECK(follow_bits_launch(A, s->timing ? s->ev0.e : nullptr, s->timing ? s->ev1.e : nullptr, st));
   HIPCHECK(follow_count_launch(A, st));
   // the batch's one host synchronisation: the completed walks and their longest span

@@ -125,6 +125,10 @@ struct cep_session {
   // the tiles' starts, the completed walks per bitmap word and their prefix, sized from max_events at open;
   // the walks' keys, their order and the sort's scratch are the runs workspace's rk, rk_sorted, r_len, rk_tmp ----
   DBuf fw_bits, fw_sum, fw_tile, fw_cnt, fw_pre;
+  // ... on a carry session (CEP_SESSION_FOLLOW_CARRY; the walks are carried in the runs path's tail pool below,
+  // records of k words): the open starts' plane, their count per word and its prefix; the continuations per
+  // (segment, slot); per carried walk of the batch's keys its outcome flags, their prefixes, the completed ones
+  DBuf fw_open, fw_ocnt, fw_opre, fw_res, fw_cdone, fw_copen, fw_cdpre, fw_copre, fw_cdx;
   // ---- staging of host-resident batches (stage_host): a pinned ring the caller's columns are copied
   // into in chunks, each chunk moved by one async copy into one packed device image; caller memory
   // that is itself pinned is copied from directly and the push waits for that copy ----
@@ -263,8 +267,17 @@ struct HostArr {
 // for an 8 MB batch (1 M records) cost 706 us per flush against ~280 us by DMA (r04 bench)
 constexpr size_t kZeroCopyMax = size_t(1) << 20;
 
-inline int tail_rw(const cep_session* s) { return 5 + int(s->pat->prog.coltypes.size()); }
-inline bool tail_session(const cep_session* s) { return s->carry && s->path == CEP_PATH_RUNS; }
+// the tail pool's sessions: runs carry sessions (records of 5 + ncols words) and follow carry sessions
+// (walks of k words)
+inline bool walk_session(const cep_session* s) { return s->carry && s->path == CEP_PATH_FOLLOW; }
+inline int tail_rw(const cep_session* s) {
+  return walk_session(s) ? s->pat->prog.follow.k : 5 + int(s->pat->prog.coltypes.size());
+}
+inline bool tail_session(const cep_session* s) { return s->carry && (s->path == CEP_PATH_RUNS || s->path == CEP_PATH_FOLLOW); }
+// the last batch left the general / runs CSR on the device (o_record ...; its match count in scal[3])
+inline bool csr_batch(const cep_session* s) {
+  return s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS || (s->last_path == CEP_PATH_FOLLOW && s->carry);
+}
 inline bool halo_session(const cep_session* s) { return s->carry && (s->path == CEP_PATH_STENCIL || s->path == CEP_PATH_CHAIN); }
 
 // ---- helpers that cross a unit boundary (push.cpp) ----

@@ -1,5 +1,6 @@
 // state.cpp -- the carried state of CEP_SESSION_CARRY sessions (cep_state_*): the general path's per-key NFA
-// blobs, the stencil path's halos and the runs path's tails; a blob in the reference's own terms.
+// blobs, the stencil path's halos, the runs path's tails and the follow path's walks; a blob in the reference's
+// own terms.
 #include <string.h>
 
 #include "session.h"
@@ -184,6 +185,10 @@ int halo_import(cep_session* s, const uint8_t* p, size_t len, uint32_t ver) {
 // a tail: int32 key id, int32 records, int32 words per record (5 + ncols), int32 0, then the records
 // (runs.hip tail records: stream position first)
 constexpr uint32_t kTailMagic = 0x5253434Bu;   // "KCSR"
+// follow carry sessions: "KCSW", the same layout over the same pool -- a record is one waiting walk of
+// k words: slots taken s, the stream positions of its s records, zeros (follow.hip)
+constexpr uint32_t kWalkMagic = 0x5753434Bu;   // "KCSW"
+uint32_t tail_magic(const cep_session* s) { return walk_session(s) ? kWalkMagic : kTailMagic; }
 int tail_download(cep_session* s, std::vector<int64_t>& tab, std::vector<int64_t>& pool) {
   tab.resize(size_t(s->opts.max_keys) * 2);
   pool.resize(size_t(s->rpool_used) * size_t(tail_rw(s)));
@@ -214,7 +219,8 @@ int tail_export(cep_session* s, int32_t key_lo, int32_t key_hi, void* buf, size_
   if ((rc = marks_section(s, key_lo, key_hi, sec))) return rc;
   out.insert(out.end(), sec.begin(), sec.end());
   const uint32_t ver = sec.empty() ? 1 : 2;
-  memcpy(&out[0], &kTailMagic, 4); memcpy(&out[4], &ver, 4); memcpy(&out[8], &s->base, 8); memcpy(&out[16], &nkeys, 4);
+  const uint32_t magic = tail_magic(s);
+  memcpy(&out[0], &magic, 4); memcpy(&out[4], &ver, 4); memcpy(&out[8], &s->base, 8); memcpy(&out[16], &nkeys, 4);
   *needed = out.size();
   if (!buf) return CEP_OK;
   if (cap < out.size()) return fail(CEP_E_ARG, "export buffer too small");
@@ -235,6 +241,12 @@ int tail_import(cep_session* s, const uint8_t* p, size_t len, uint32_t ver) {
     if (rw != int32_t(RW)) return fail(CEP_E_ARG, "state blob does not match this pattern");
     if (k < 0 || k >= s->opts.max_keys || cnt <= 0 || at + 16 + size_t(cnt) * RW * 8 > len)
       return fail(CEP_E_ARG, "bad key entry in the state blob");
+    if (walk_session(s))                             // every walk's slot count names words of its own
+      for (int32_t j = 0; j < cnt; j++) {
+        int64_t sl;
+        memcpy(&sl, p + at + 16 + size_t(j) * RW * 8, 8);
+        if (sl < 1 || sl >= int64_t(RW)) return fail(CEP_E_ARG, "bad walk in the state blob");
+      }
     ents.push_back({k, at});
     recs += size_t(cnt);
     at += 16 + size_t(cnt) * RW * 8;
@@ -318,8 +330,9 @@ int cep_state_import(cep_session* s, const void* buf, size_t len) {
     return halo_import(s, p, len, ver);
   }
   if (tail_session(s)) {
-    if (magic != kTailMagic || (ver != 1 && ver != 2) || nkeys < 0)
-      return fail(CEP_E_ARG, "bad state blob (runs sessions take KCSR)");
+    if (magic != tail_magic(s) || (ver != 1 && ver != 2) || nkeys < 0)
+      return fail(CEP_E_ARG, walk_session(s) ? "bad state blob (follow carry sessions take KCSW)"
+                                             : "bad state blob (runs sessions take KCSR)");
     return tail_import(s, p, len, ver);
   }
   if (magic != kStateMagic || ver != 1 || nkeys < 0) return fail(CEP_E_ARG, "bad state blob");
@@ -393,6 +406,8 @@ int cep_key_state(cep_session* s, int32_t key, int64_t* runs, int64_t* queue_len
   if (!runs || !queue_len || key < 0 || key >= s->opts.max_keys) return fail(CEP_E_ARG, "bad argument");
   if (halo_session(s))
     return fail(CEP_E_UNSUPPORTED, "a stencil carry session keeps each key's last records, not its NFA runs");
+  if (walk_session(s))
+    return fail(CEP_E_UNSUPPORTED, "a follow carry session keeps each key's waiting walks, not its NFA queue");
   if (tail_session(s))
     return fail(CEP_E_UNSUPPORTED, "a runs carry session keeps each key's records from its oldest open run, not its NFA queue");
   if ((rc = drain(s))) return rc;
@@ -475,7 +490,7 @@ int cep_state_evict(cep_session* s, const int32_t* keys, int64_t n, const uint8_
     if (rc2) return rc2;
     for (int64_t i = 0; i < n; i++) {
       const bool hm = has_marks(keys[i]), ht = tab[2 * size_t(keys[i]) + 1] > 0;
-      if (ht || hm) header(kTailMagic, ht ? 1 : 0, hm ? 2 : 1);
+      if (ht || hm) header(tail_magic(s), ht ? 1 : 0, hm ? 2 : 1);
       if (ht) tail_entry(s, tab, pool, keys[i], out);
       if (hm) marks_out(keys[i]);
       tab[2 * size_t(keys[i]) + 1] = 0;              // (the pool records are reclaimed by the next compaction)
@@ -655,7 +670,7 @@ int cep_state_import_keys(cep_session* s, const void* const* blobs, const size_t
   if (n < 0 || (n > 0 && (!blobs || !lens || !keys))) return fail(CEP_E_ARG, "null argument");
   // one multi-key blob with the keys renumbered, then the ordinary import
   std::vector<uint8_t> all(20), msec(4);           // msec: the blobs' marks, re-keyed (version 2 blobs)
-  const uint32_t magic = halo_session(s) ? kHaloMagic : tail_session(s) ? kTailMagic : kStateMagic;
+  const uint32_t magic = halo_session(s) ? kHaloMagic : tail_session(s) ? tail_magic(s) : kStateMagic;
   int64_t base = 0;
   int32_t nk = 0, nmarks = 0;
   for (int64_t i = 0; i < n; i++) {
@@ -677,8 +692,9 @@ int cep_state_import_keys(cep_session* s, const void* const* blobs, const size_t
         int32_t w = 0, rw = 1;
         if (lens[i] < 36) return fail(CEP_E_ARG, "truncated state blob");
         memcpy(&w, p + 24, 4); memcpy(&rw, p + 28, 4);
-        if (w < 0 || (magic == kTailMagic && rw < 0)) return fail(CEP_E_ARG, "bad key entry in the state blob");
-        end = 36 + 8 * size_t(w) * (magic == kTailMagic ? size_t(rw) : 1);
+        const bool tail = magic == kTailMagic || magic == kWalkMagic;
+        if (w < 0 || (tail && rw < 0)) return fail(CEP_E_ARG, "bad key entry in the state blob");
+        end = 36 + 8 * size_t(w) * (tail ? size_t(rw) : 1);
       }
       const int64_t mc = end <= lens[i] ? marks_parse(p, end, lens[i]) : -1;
       if (mc < 0) return fail(CEP_E_ARG, "truncated marks section in the state blob");
@@ -708,7 +724,8 @@ int cep_state_positions(const void* buf, size_t len, int64_t* out, int64_t cap, 
   uint32_t magic, ver;
   int32_t nkeys;
   memcpy(&magic, p, 4); memcpy(&ver, p + 4, 4); memcpy(&nkeys, p + 16, 4);
-  if ((magic != kStateMagic && magic != kHaloMagic && magic != kTailMagic) || nkeys < 0) return fail(CEP_E_ARG, "bad state blob");
+  if ((magic != kStateMagic && magic != kHaloMagic && magic != kTailMagic && magic != kWalkMagic) || nkeys < 0)
+    return fail(CEP_E_ARG, "bad state blob");
   int64_t cnt = 0;
   size_t at = 20;
   auto put = [&](int64_t v) { if (out && cnt < cap) out[cnt] = v; cnt++; };
@@ -725,6 +742,24 @@ int cep_state_positions(const void* buf, size_t len, int64_t* out, int64_t cap, 
         int64_t v;
         memcpy(&v, p + at + 16 + size_t(j) * size_t(rw) * 8, 8);
         put(v);
+      }
+      at += 16 + size_t(w) * size_t(rw) * 8;
+      continue;
+    }
+    if (magic == kWalkMagic) {                       // key, walks, words per walk, 0, walks (slots taken, their positions)
+      int32_t rw;
+      if (at + 16 > len) return fail(CEP_E_ARG, "truncated state blob");
+      memcpy(&rw, p + at + 8, 4);
+      if (w <= 0 || rw < 2 || at + 16 + size_t(w) * size_t(rw) * 8 > len) return fail(CEP_E_ARG, "truncated state blob");
+      for (int32_t j = 0; j < w; j++) {
+        const uint8_t* walk = p + at + 16 + size_t(j) * size_t(rw) * 8;
+        int64_t sl, v;
+        memcpy(&sl, walk, 8);
+        if (sl < 1 || sl >= rw) return fail(CEP_E_ARG, "bad walk in the state blob");
+        for (int64_t q = 1; q <= sl; q++) {
+          memcpy(&v, walk + 8 * q, 8);
+          put(v);
+        }
       }
       at += 16 + size_t(w) * size_t(rw) * 8;
       continue;

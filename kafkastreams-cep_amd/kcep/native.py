@@ -39,6 +39,7 @@ SESSION_LANE_NFA = 8
 SESSION_WAVE_NFA = 16
 SESSION_MASK_PASS = 32     # opt-in: stencil / chain path for eligible multi-column predicates (CompiledPattern.mask_pass)
 SESSION_FOLLOW = 64        # opt-in: the follow path for eligible skip-till-next patterns (CompiledPattern.follow)
+SESSION_FOLLOW_CARRY = 128  # ... on carry sessions too: the waiting walks carried per key (implies SESSION_FOLLOW)
 
 
 class CepError(RuntimeError):
@@ -288,7 +289,7 @@ class Session:
 
     def __init__(self, pattern: CompiledPattern, max_events: int, mode=MODE_PROCESSOR, device=0, force_path=0,
                  carry=False, max_keys=0, interpret=False, profile=False, max_key_words=0, lane_nfa=None,
-                 max_pool_bytes=0, mask_pass=False, follow=False):
+                 max_pool_bytes=0, mask_pass=False, follow=False, follow_carry=False):
         """``carry=True``: every key's NFA state continues across batches (CEP_SESSION_CARRY);
         key ids must then be dense in [0, max_keys) and record positions are stream positions.
         ``interpret=True``: the built-in interpreting kernels instead of kernels compiled for the
@@ -301,14 +302,16 @@ class Session:
         path, a pre-pass kernel writing each record's stage mask; no effect on any other pattern.
         ``follow=True`` (CEP_SESSION_FOLLOW): a pattern of strict and skip-till-next stages
         (``CompiledPattern.follow``) opens on the follow path instead of the general NFA; no effect on any
-        other pattern, nor with ``carry=True``."""
+        other pattern, nor with ``carry=True``.
+        ``follow_carry=True`` (CEP_SESSION_FOLLOW_CARRY): the same with ``carry=True`` too -- the session
+        carries every key's waiting walks ("KCSW" state blobs), batches follow the runs carry rules."""
         self.pattern = pattern
         self.h = C.c_void_p()
         # lane_nfa: None = the library's choice, True = one key per lane, False = one key per wave
         flags = ((SESSION_CARRY if carry else 0) | (SESSION_INTERPRET if interpret else 0) |
                  (SESSION_PROFILE if profile else 0) | (SESSION_LANE_NFA if lane_nfa else 0) |
                  (SESSION_WAVE_NFA if lane_nfa is False else 0) | (SESSION_MASK_PASS if mask_pass else 0) |
-                 (SESSION_FOLLOW if follow else 0))
+                 (SESSION_FOLLOW if follow else 0) | (SESSION_FOLLOW_CARRY if follow_carry else 0))
         o = Opts(device, mode, force_path, flags, max_events, max_keys, 0.0, max_key_words, max_pool_bytes)
         check(lib().cep_session_open(pattern.h, C.byref(o), C.byref(self.h)))
         self.path = lib().cep_session_path(self.h)

@@ -109,7 +109,8 @@ class GpuCEPProcessor:
     def __init__(self, queryName: str, pattern: Union[Pattern, bytes], schema: Schema, decoder: ColumnDecoder,
                  batch_size: int = 1 << 16, max_keys: int = 1 << 20, device: int = 0,
                  mode: int = N.MODE_PROCESSOR, prune_at: int = 1 << 20, max_key_words: int = 0,
-                 stop_at_error: bool = False, device_filter: bool = False, mask_pass: bool = False):
+                 stop_at_error: bool = False, device_filter: bool = False, mask_pass: bool = False,
+                 follow: bool = False):
         if decoder.schema is not schema and decoder.schema.columns != schema.columns:
             raise ValueError("decoder and pattern use different schemas")
         self.queryName = queryName.lower().replace("\\s+", "")
@@ -129,6 +130,10 @@ class GpuCEPProcessor:
         # CEP_SESSION_MASK_PASS for the session init() opens: an eligible multi-column strict pattern then
         # runs on the stencil / chain path (native.CompiledPattern.mask_pass); no effect on other patterns
         self.mask_pass = bool(mask_pass)
+        # CEP_SESSION_FOLLOW_CARRY for the session init() opens: an eligible pattern of strict and
+        # skip-till-next stages then runs on the follow path (native.CompiledPattern.follow), which takes
+        # batches as the runs path does; no effect on other patterns
+        self.follow = bool(follow)
         self.device = device
         self.mode = mode
         ir = pattern if isinstance(pattern, (bytes, bytearray)) else pattern.to_ir(schema)
@@ -163,7 +168,8 @@ class GpuCEPProcessor:
         self._forward = forward
         self.session = session or N.Session(self.compiled, self.batch_size, mode=self.mode, device=self.device,
                                             carry=True, max_keys=self.max_keys, max_key_words=self.max_key_words,
-                                            mask_pass=self.mask_pass)
+                                            mask_pass=self.mask_pass,
+                                            **({"follow_carry": True} if self.follow else {}))
 
     def process(self, key, value, topic: str, partition: int, offset: int, timestamp: int):
         """One record with its ``ProcessorContext`` metadata."""
@@ -286,9 +292,9 @@ class GpuCEPProcessor:
         self._arrived += len(recs)
         arrival = list(range(len(recs)))                  # the processor-wide arrival index of recs[i] is base + this
         self._flags = 0
-        if self.device_filter and self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS):
+        if self.device_filter and self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS, N.PATH_FOLLOW):
             self._flags = N.BATCH_FILTER                  # every record goes: arrival stays the identity
-        elif self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS):
+        elif self.session.path in (N.PATH_STENCIL, N.PATH_CHAIN, N.PATH_RUNS, N.PATH_FOLLOW):
             # the stencil / chain / runs paths carry each key's records (its last K-1, or those
             # from its oldest open run on), not its NFA: the high-water-mark rule
             # (CEPProcessor.checkHighWaterMark :152-160) is applied here, in arrival order, and the
