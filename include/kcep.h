@@ -202,7 +202,23 @@ typedef struct {
                                     streaming bitmap kernel, cep_last_batch_ms the whole push, which waits once
                                     for the match count.  The flag does nothing for a pattern that is not
                                     eligible, so a host may set it unconditionally.  Without the flag every
-                                    pattern opens on the path it always did. */
+                                    pattern opens on the path it always did.
+                                    With CEP_SESSION_MASK_PASS the path also takes, in its evaluated form, a
+                                    pattern of the shape above (the first three conditions) whose predicates
+                                    the direct lowering does not take -- several columns, arithmetic, event
+                                    metadata -- when every predicate, with its topic filter, reads nothing but
+                                    the current record and cannot raise (the rule of CEP_SESSION_MASK_PASS;
+                                    cep_pattern_follow_mask).  The streaming kernel then evaluates every
+                                    predicate on every record from the columns it reads, straight into the
+                                    bitmaps: compiled for the pattern unless CEP_SESSION_INTERPRET / KCEP_JIT=0
+                                    (cep_session_jit).  A pattern the direct form takes keeps the direct form.
+                                    The automatic choice stays stencil / chain (direct, mask-pass), follow
+                                    (direct, evaluated), runs, general; force_path = CEP_PATH_FOLLOW opens such
+                                    a pattern only with CEP_SESSION_MASK_PASS set and fails as without it
+                                    otherwise.  Everything else is a follow session; device-resident columns
+                                    and metadata arrays the predicates read must be 16-byte aligned, as the
+                                    key.  With only one of the two flags every pattern opens where it opens
+                                    with that flag alone. */
 
 #define CEP_SESSION_FOLLOW_CARRY 128 /* opt-in: the follow path on CEP_SESSION_CARRY sessions too.  Implies
                                     CEP_SESSION_FOLLOW; without CEP_SESSION_CARRY it is that flag.  A carry
@@ -221,9 +237,14 @@ typedef struct {
                                     that fails its key checks leaves the walks and the marks untouched.
                                     cep_state_* work as on a runs carry session with "KCSW" blobs (KCSR / KCST
                                     blobs are refused with CEP_E_ARG); cep_state_positions of one returns every
-                                    walk's s positions; cep_key_state fails with CEP_E_UNSUPPORTED.  Not
-                                    composed with CEP_SESSION_MASK_PASS.  The flag does nothing for a pattern
-                                    that is not eligible. */
+                                    walk's s positions; cep_key_state fails with CEP_E_UNSUPPORTED.
+                                    With CEP_SESSION_MASK_PASS a carry session also takes a pattern in the
+                                    path's evaluated form (cep_pattern_follow_mask, see CEP_SESSION_FOLLOW):
+                                    only the source of the bitmaps changes, the carried walks, the batch rules
+                                    and the KCSW blobs are the same, and a ts / offset the batch does not give
+                                    is the record's stream position; device-resident columns and metadata
+                                    arrays the predicates read must be 16-byte aligned.  The flag does nothing
+                                    for a pattern that is not eligible. */
 
 #define CEP_MEM_HOST 0
 #define CEP_MEM_DEVICE 1
@@ -368,6 +389,12 @@ int cep_pattern_mask_pass(const cep_pattern* p, int32_t* k, int32_t* chain);
  * stage counts n), bit s of *next_mask = slot s is skip-till-next; the outputs may be NULL.  Else
  * CEP_E_UNSUPPORTED with the reason in cep_last_error.  Host-only, as cep_pattern_mask_pass. */
 int cep_pattern_follow(const cep_pattern* p, int32_t* k, uint32_t* next_mask);
+/* CEP_OK if the pattern takes the follow path in its evaluated form (CEP_SESSION_MASK_PASS together with
+ * CEP_SESSION_FOLLOW / CEP_SESSION_FOLLOW_CARRY): the shape cep_pattern_follow asks for, predicates its lowering
+ * does not take, every one total and event-only as for cep_pattern_mask_pass.  Outputs as cep_pattern_follow;
+ * else CEP_E_UNSUPPORTED with the reason in cep_last_error (a pattern cep_pattern_follow takes is not eligible:
+ * it keeps the direct form).  Host-only. */
+int cep_pattern_follow_mask(const cep_pattern* p, int32_t* k, uint32_t* next_mask);
 
 /* --- session: one per stream task (CEPProcessor.init :88-108) --- */
 int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** out);

@@ -156,9 +156,13 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   // CEP_SESSION_FOLLOW: an eligible pattern's skip-till-next walks, on sessions without carry;
   // CEP_SESSION_FOLLOW_CARRY: on carry sessions too (the waiting walks carried per key), and implies the former
   const bool follow_carry = (opts->flags & CEP_SESSION_FOLLOW_CARRY) != 0;
-  const bool follow_flag = (((opts->flags & CEP_SESSION_FOLLOW) && !carry) || follow_carry) && P.follow_ok;
+  // ... with CEP_SESSION_MASK_PASS also a pattern of the follow shape whose predicates the direct lowering does
+  // not take (cep_pattern_follow_mask), in the evaluated form
+  const bool follow_eval = (opts->flags & CEP_SESSION_MASK_PASS) && P.follow_mask_ok;
+  const bool follow_flag =
+      (((opts->flags & CEP_SESSION_FOLLOW) && !carry) || follow_carry) && (P.follow_ok || follow_eval);
   if (path == 0) path = sp ? fast : follow_flag ? CEP_PATH_FOLLOW : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
-  if (path == CEP_PATH_FOLLOW && !P.follow_ok)
+  if (path == CEP_PATH_FOLLOW && !P.follow_ok && !follow_eval)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: " + P.follow_why);
   if (path == CEP_PATH_FOLLOW && carry && !follow_carry)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: it takes sessions without CEP_SESSION_CARRY");
@@ -183,7 +187,11 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->pat = p;
   s->opts = *opts;
   s->path = path;
-  s->sp = follow ? &P.follow : sp ? sp : &P.stencil;   // (never null: a collect before any push reads its k)
+  s->follow_eval = follow && !P.follow_ok;          // (a pattern the direct lowering takes keeps it)
+  s->follow_split = s->follow_eval && getenv_flag("KCEP_FOLLOW_MASK_SPLIT");
+  s->follow_next = s->follow_eval ? P.follow_mask_next : P.follow_next;
+  // (never null: a collect before any push reads its k)
+  s->sp = follow ? (s->follow_eval ? &P.follow_mask : &P.follow) : sp ? sp : &P.stencil;
   s->mask_pass = masked && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN);
   s->device = opts->device;
   auto cleanup = [&](int rc) {
@@ -196,7 +204,7 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   if (follow) {
     // the rows of a stencil session without carry (a start completes at most once: cap rows), and the
     // bitmaps of follow.hip for a batch of max_events
-    const StencilProgram& FP = P.follow;
+    const StencilProgram& FP = *s->sp;
     const size_t nt = size_t(follow_tiles(cap)), planes = size_t(FP.k) + 1;
     if (s->prog.ensure(sizeof(StencilProgram)) || s->total.ensure(64) || s->sum.ensure(64) ||
         (!carry && s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap))) || s->fw_bits.ensure(planes * nt * 64 * 8) ||
@@ -208,6 +216,12 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
     s->out_cap = cap;
     if (hipMemcpy(s->prog.p, &FP, sizeof(StencilProgram), hipMemcpyHostToDevice) || hipMemset(s->total.p, 0, s->total.cap))
       return cleanup(fail(CEP_E_HIP, "device init failed"));
+    // the evaluated form: the slots' bytecode for the streaming kernel; the split form's mask column
+    if (s->follow_eval &&
+        (s->mprog.ensure(sizeof(MaskProgram)) ||
+         (s->follow_split && s->mcol.ensure(sizeof(int32_t) * size_t((cap + 3) & ~int64_t(3)))) ||
+         hipMemcpy(s->mprog.p, &P.follow_mask_prog, sizeof(MaskProgram), hipMemcpyHostToDevice)))
+      return cleanup(fail(CEP_E_HIP, "device allocation failed"));
   }
   if (sp && path != CEP_PATH_GENERAL && !follow) {
     const int k = sp->k;
@@ -279,6 +293,7 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->jit_on = !(opts->flags & CEP_SESSION_INTERPRET) && !(env_jit && !strcmp(env_jit, "0"));
   if (s->jit_on && path == CEP_PATH_RUNS) s->jit = jit_runs(P, s->jit_why);   // on failure: built-in kernels
   if (s->jit_on && s->mask_pass) s->jitm = jit_masks(P, s->jit_why);        // on failure: the built-in kernel
+  if (s->jit_on && s->follow_eval) s->jitm = s->follow_split ? jit_masks(P, s->jit_why, true) : jit_follow_bits(P, s->jit_why);
   if (s->jit_on && path == CEP_PATH_GENERAL) {
     s->jitg = jit_general(P, s->jit_why, s->opts.flags & CEP_SESSION_PROFILE);
     s->jitg_tried = true;
@@ -332,7 +347,8 @@ int cep_key_profile(cep_session* s, int64_t* out, int64_t cap, int64_t* n_keys) 
 
 int cep_session_jit(const cep_session* s) {
   if (!s) return 0;
-  return (s->path == CEP_PATH_RUNS && s->jit) || (s->path == CEP_PATH_GENERAL && s->jitg) || (s->mask_pass && s->jitm) ? 1 : 0;
+  const bool masks = (s->mask_pass || s->follow_eval) && s->jitm;
+  return (s->path == CEP_PATH_RUNS && s->jit) || (s->path == CEP_PATH_GENERAL && s->jitg) || masks ? 1 : 0;
 }
 
 int cep_session_wave(const cep_session* s) { return s && s->path == CEP_PATH_GENERAL && s->wave ? 1 : 0; }
@@ -375,14 +391,26 @@ int cep_pattern_follow(const cep_pattern* p, int32_t* k, uint32_t* next_mask) {
   return CEP_OK;
 }
 
+int cep_pattern_follow_mask(const cep_pattern* p, int32_t* k, uint32_t* next_mask) {
+  if (!p) return fail(CEP_E_ARG, "null argument");
+  const Program& P = p->prog;
+  if (!P.follow_mask_ok) return fail(CEP_E_UNSUPPORTED, "follow path's evaluated form does not apply: " + P.follow_mask_why);
+  if (k) *k = P.follow_mask.k;
+  if (next_mask) *next_mask = P.follow_mask_next;
+  return CEP_OK;
+}
+
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed) {
   if (!p || !needed) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
   const bool masks = mask_pass_path(p->prog, path);
-  if (!runs && !general && !masks) return no_kernels(p->prog, path);
+  const bool fbits = path == CEP_PATH_FOLLOW && p->prog.follow_mask_ok;   // the follow path's evaluated form
+  if (!runs && !general && !masks && !fbits) return no_kernels(p->prog, path);
   std::string why;
-  const std::string src = masks ? jit_source_masks(p->prog, why)
-                                : runs ? jit_source_runs(p->prog, why) : jit_source_general(p->prog, why);
+  const std::string src = fbits   ? jit_source_follow_bits(p->prog, why)
+                          : masks ? jit_source_masks(p->prog, why)
+                          : runs  ? jit_source_runs(p->prog, why)
+                                  : jit_source_general(p->prog, why);
   if (src.empty()) return fail(CEP_E_UNSUPPORTED, "kernel generation failed: " + why);
   *needed = src.size() + 1;
   if (!buf) return CEP_OK;
@@ -395,9 +423,13 @@ int cep_pattern_build_kernels(const cep_pattern* p, int path) {
   if (!p) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
   const bool masks = mask_pass_path(p->prog, path);
-  if (!runs && !general && !masks) return no_kernels(p->prog, path);
+  const bool fbits = path == CEP_PATH_FOLLOW && p->prog.follow_mask_ok;
+  if (!runs && !general && !masks && !fbits) return no_kernels(p->prog, path);
   std::string why;
-  if (!(masks ? jit_check_masks(p->prog, why) : runs ? jit_check_runs(p->prog, why) : jit_check_general(p->prog, why)))
+  if (!(fbits   ? jit_check_follow_bits(p->prog, why)
+        : masks ? jit_check_masks(p->prog, why)
+        : runs  ? jit_check_runs(p->prog, why)
+                : jit_check_general(p->prog, why)))
     return fail(CEP_E_UNSUPPORTED, "kernel build failed: " + why);
   return CEP_OK;
 }

@@ -614,14 +614,13 @@ void analyse_runs(Program& P) {
 // a strict slot takes the next record of the key or the run dies, a skip-till-next slot the key's next
 // record satisfying it -- and emits at most one match.  The slots (a times(n) stage is n of them) are
 // lowered as analyse_stencil lowers stages; bit s of follow_next: slot s is skip-till-next.
-void analyse_follow(Program& P) {
-  auto no = [&](const std::string& w) { P.follow_ok = false; P.follow_why = w; };
-  StencilProgram& S = P.follow;
-  memset(&S, 0, sizeof S);
-  P.follow_next = 0;
+// the shape both forms of the path take (analyse_follow, analyse_follow_mask): K = the slots, bit s of next:
+// slot s is skip-till-next
+bool follow_shape(const Program& P, int& K, uint32_t& next, std::string& why) {
+  auto no = [&](const std::string& w) { why = w; return false; };
   const int np = int(P.pats.size());
-  int K = 0;
-  bool any_next = false;
+  K = 0;
+  next = 0;
   for (int i = 0; i < np; i++) {
     const auto& p = P.pats[i];
     if (p.one_or_more) return no(p.optional ? "zeroOrMore stage" : "oneOrMore stage");
@@ -634,14 +633,28 @@ void analyse_follow(Program& P) {
     if (i == 0 && p.strategy != S_STRICT) return no("non-strict first stage");
     if (i == 0 && p.times > 1) return no("times on the first stage");
     if (p.times < 1) return no("times below 1");
-    K += p.times;
-    if (K > STENCIL_MAX_K) return no("more than 8 slots (stages, a times(n) stage counting n)");
-    any_next = any_next || p.strategy == S_NEXT;
+    if (K + p.times > STENCIL_MAX_K) return no("more than 8 slots (stages, a times(n) stage counting n)");
+    for (int r = 0; r < p.times; r++, K++)
+      if (p.strategy == S_NEXT) next |= 1u << K;
   }
-  if (!any_next)
+  if (!next)
     return no(std::string("no skip-till-next stage: ") + (P.stencil_ok ? "the stencil path takes the pattern"
                                                           : P.runs_ok  ? "the runs path takes the pattern"
                                                                        : "the pattern keeps its path"));
+  return true;
+}
+
+void analyse_follow(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_ok = false; P.follow_why = w; };
+  StencilProgram& S = P.follow;
+  memset(&S, 0, sizeof S);
+  P.follow_next = 0;
+  const int np = int(P.pats.size());
+  int K = 0;
+  {
+    std::string why;
+    if (!follow_shape(P, K, P.follow_next, why)) return no(why);
+  }
   Lowering L;
   S.k = K;
   for (int i = 0, slot = 0; i < np && L.ok; i++) {
@@ -652,7 +665,6 @@ void analyse_follow(Program& P) {
     for (int r = 0; r < p.times; r++, slot++) {
       S.name[slot] = p.name_id;
       put_slot(S, slot, d);
-      if (p.strategy == S_NEXT) P.follow_next |= 1u << slot;
     }
   }
   if (!L.ok) return no(L.why);
@@ -892,6 +904,60 @@ void analyse_mask_pass(Program& P) {
   P.mask_why.clear();
 }
 
+// Evaluated form of the follow path (kcep_internal.h Program::follow_mask_ok): the shape of analyse_follow,
+// predicates its lowering does not take, every stage predicate event-only and total (the rule of
+// analyse_mask_pass: the streaming kernel evaluates a slot on every record).  The n slots of a times(n)
+// stage share one code offset.
+void analyse_follow_mask(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_mask_ok = false; P.follow_mask_why = w; };
+  StencilProgram& S = P.follow_mask;
+  MaskProgram& M = P.follow_mask_prog;
+  memset(&S, 0, sizeof S);
+  memset(&M, 0, sizeof M);
+  P.follow_mask_next = 0;
+  int K = 0;
+  {
+    std::string why;
+    if (!follow_shape(P, K, P.follow_mask_next, why)) return no(why);
+  }
+  if (P.follow_ok) return no("the pattern lowers to the follow path directly");
+  if (P.coltypes.size() > 16) return no("too many columns");
+  static_assert(MASK_SLOTS == STENCIL_MAX_K, "a slot of the follow path is a slot of the mask program");
+  CodeGen cg;
+  cg.names = &P.names;
+  int slot = 0;
+  for (const auto& p : P.pats) {
+    const ExprP pred = p.topic >= 0 ? mk(OP_AND, mk_topic(p.topic), p.pred) : p.pred;
+    if (const char* unfit = mask_unfit(pred)) return no(unfit);
+    if (!event_only(pred)) return no("predicate reads more than the current record");
+    mask_reads(pred, M);
+    const int pc = cg.emit(pred);
+    for (int r = 0; r < p.times; r++, slot++) {
+      S.name[slot] = p.name_id;
+      M.pslots |= 1 << slot;
+      M.pc[slot] = pc;
+    }
+  }
+  if (!cg.ok) return no(cg.why);
+  if (cg.maxdepth > NFA_STACK) return no("expression nests deeper than the device operand stack");
+  if (cg.code.size() > size_t(NFA_MAX_CODE)) return no("predicate code too large");
+  M.ncols = int32_t(P.coltypes.size());
+  for (size_t c = 0; c < P.coltypes.size(); c++) M.coltype[c] = P.coltypes[c];
+  M.ncode = int32_t(cg.code.size());
+  memcpy(M.code, cg.code.data(), cg.code.size() * sizeof(int32_t));
+  // k and the names are what the walks' row kernels and cep_collect read; the identity table makes it the
+  // program follow_bits reads a mask column through (KCEP_FOLLOW_MASK_SPLIT=1)
+  S.k = K;
+  S.pslots = M.pslots;
+  S.col = -1;
+  S.coltype = T_I32;
+  S.lut_lo = 0;
+  S.lut_n = 256;
+  for (int m = 0; m < 256; m++) S.lut[1 + m] = uint8_t(m);
+  P.follow_mask_ok = true;
+  P.follow_mask_why.clear();
+}
+
 }  // namespace
 
 int lower_general(Program& P, std::string& why) {
@@ -1036,6 +1102,7 @@ int compile_ir(const uint8_t* ir, size_t len, Program& P, std::string& err) {
   analyse_runs(P);
   analyse_mask_pass(P);
   analyse_follow(P);
+  analyse_follow_mask(P);
   P.has_seq = false;
   for (const auto& pd : P.pats) {
     P.has_seq = P.has_seq || uses_seq(pd.pred);

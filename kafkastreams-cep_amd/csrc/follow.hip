@@ -9,6 +9,9 @@
 //                 the stencil kernels compute them; out: one bitmap per slot (bit p: record p satisfies
 //                 the slot), one of key starts (key[p] != key[p - 1]), a second level over each (bit w:
 //                 word w is not zero) and per tile the number of starts -- (K + 1) / 8 B per record
+//   follow_eval_bits  the same planes where the predicates read several columns, arithmetic or metadata
+//                 (the evaluated form, follow_bits_dev.h): the key and the columns they read, each slot
+//                 evaluated per record; interpreted here, compiled per pattern by jit.cpp
 //   follow_count  a wave per word of slot 0's bitmap, a lane per set bit: walks, counts the completed
 //   (scan)        exclusive_scan over the words' counts (scan.hip)
 //   follow_write  the same walks again (the bitmaps of a flush-sized batch sit in L2): the completed
@@ -19,14 +22,15 @@
 // A strict hop is one bit test; a skip-till-next hop and the end of the start's key segment are a
 // find-next-set-bit: the rest of the current word, then second-level words, then one first-level word,
 // <= 2 + gap / 4096 word reads.
+#include "follow_bits_dev.h"
 #include "stencil_kernel.h"
 
 namespace kcep {
 
 static_assert(FOLLOW_TILE == ST_TILE, "follow_bits takes the stencil kernels' tile: one chunk per thread");
 static_assert(FOLLOW_TILE == 64 * 64, "a tile is 64 bitmap words: one second-level word");
-
-typedef unsigned long long u64;
+static_assert(FB_TILE == FOLLOW_TILE && FB_THREADS == ST_THREADS && FB_MAX_K == STENCIL_MAX_K,
+              "follow_bits_dev.h's tile is follow_bits' tile");
 
 int64_t follow_tiles(int64_t n) { return (std::max<int64_t>(n, 1) + FOLLOW_TILE - 1) / FOLLOW_TILE; }
 
@@ -220,6 +224,14 @@ __global__ __launch_bounds__(ST_THREADS) void follow_bits(const int32_t* __restr
   if (tid == 0) tile_starts[tile] = int64_t(s_cnt[0]) + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
+// ---- follow_eval_bits: the evaluated form's streaming kernel (follow_bits_dev.h), the slots interpreted;
+// jit.cpp compiles the same body per pattern (kcep_follow_bits) ----
+__global__ __launch_bounds__(FB_THREADS) void follow_eval_bits(MaskArgs A, int k, u64* __restrict__ bits,
+                                                              u64* __restrict__ sum, int64_t wpl, int64_t nt,
+                                                              int64_t* __restrict__ tile_starts) {
+  follow_eval_bits_body(FollowInterpTab{{A.P}}, A, k, bits, sum, wpl, nt, tile_starts);
+}
+
 // ---- follow_count / follow_write: a workgroup per tile, each wave 16 words of slot 0's bitmap ----
 // CARRY (count pass of a carry session): also the starts whose walk is open at the batch end, as a bitmap
 // plane (open) and per word a count (wopen)
@@ -319,6 +331,30 @@ hipError_t follow_bits_launch(const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev
   else bits_launch<double>(A, st);
   if (ev1) (void)hipEventRecord(ev1, st);
   return hipGetLastError();
+}
+
+// the evaluated form: M the columns the slots read (push.cpp), A the planes; jf: the per-pattern kernel, or null
+hipError_t follow_eval_bits_launch(const MaskArgs& M, const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st,
+                                   hipFunction_t jf) {
+  if (A.n <= 0 || M.n != A.n || A.k < 2 || A.k > STENCIL_MAX_K) return hipErrorInvalidValue;
+  const int64_t nt = follow_tiles(A.n);
+  if (ev0) (void)hipEventRecord(ev0, st);
+  hipError_t e = hipSuccess;
+  if (jf) {
+    MaskArgs m = M;
+    int k = A.k;
+    u64 *bits = A.bits, *sum = A.sum;
+    int64_t wpl = nt * 64, ntv = nt;
+    int64_t* ts = A.tile_starts;
+    void* args[] = {&m, &k, &bits, &sum, &wpl, &ntv, &ts};
+    e = hipModuleLaunchKernel(jf, unsigned(nt), 1, 1, FB_THREADS, 1, 1, 0, st, args, nullptr);
+  } else {
+    hipLaunchKernelGGL(follow_eval_bits, dim3(unsigned(nt)), dim3(FB_THREADS), 0, st, M, A.k, A.bits, A.sum, nt * 64, nt,
+                       A.tile_starts);
+    e = hipGetLastError();
+  }
+  if (ev1) (void)hipEventRecord(ev1, st);
+  return e;
 }
 
 // the completed walks counted per word of slot 0's bitmap, the counts' prefix, their number (*nm) and

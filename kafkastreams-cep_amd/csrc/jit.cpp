@@ -465,9 +465,10 @@ std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why,
 
 // The mask pre-pass (masks_dev.h): the MaskProgram's small fields as a constant (code[] stays zero: the
 // slots are compiled), one function per slot, and the kernel of masks.hip's shape around them.
-std::string jit_source_masks(const Program& P, std::string& why) {
-  if (!P.mask_ok) { why = "the pattern is not mask-pass eligible: " + P.mask_why; return ""; }
-  const MaskProgram& m = P.mask_prog;
+namespace {
+// the table a mask program's kernels are built around (members: what the body reads of it beyond NC, prog
+// and eval); tail: the header with the body, and the kernel
+std::string mask_tab_source(const MaskProgram& m, const char* members, const char* tail, std::string& why) {
   std::string o = "#include \"interp.h\"\nnamespace kcep {\n";
   o += "constexpr MaskProgram kcep_mask_prog = {" + std::to_string(m.pslots) + ",";
   put_arr(o, m.pc, MASK_SLOTS);
@@ -484,21 +485,32 @@ std::string jit_source_masks(const Program& P, std::string& why) {
   o += "  }\n  return false;\n}\n";
   o += R"(struct MaskJitTab {
   static constexpr int NC = 16;                   // every column read is held in registers (constant indices)
-  __device__ __forceinline__ const MaskProgram& prog() const { return kcep_mask_prog; }
+)";
+  o += members;
+  o += R"(  __device__ __forceinline__ const MaskProgram& prog() const { return kcep_mask_prog; }
   template <class Env>
   __device__ __forceinline__ bool eval(int pc, Env& env, int64_t& v) const { return jit_eval(pc, env, v); }
 };
 }  // namespace kcep
-#include "masks_dev.h"
+)";
+  o += tail;
+  return o;
+}
+}  // namespace
+
+// follow: the pre-pass of a pattern in the evaluated follow form (a KCEP_FOLLOW_MASK_SPLIT=1 session)
+std::string jit_source_masks(const Program& P, std::string& why, bool follow) {
+  if (!follow && !P.mask_ok) { why = "the pattern is not mask-pass eligible: " + P.mask_why; return ""; }
+  if (follow && !P.follow_mask_ok) { why = "the follow path's evaluated form does not apply: " + P.follow_mask_why; return ""; }
+  return mask_tab_source(follow ? P.follow_mask_prog : P.mask_prog, "", R"(#include "masks_dev.h"
 extern "C" __global__ __launch_bounds__(kcep::MK_THREADS) void kcep_masks(kcep::MaskArgs A) {
   kcep::masks_body(kcep::MaskJitTab{}, A);
 }
-)";
-  return o;
+)", why);
 }
 
-std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why) {
-  const std::string src = jit_source_masks(P, why);
+std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why, bool follow) {
+  const std::string src = jit_source_masks(P, why, follow);
   if (src.empty()) return nullptr;
   static const char* const names[] = {"kcep_masks"};
   static hipFunction_t JitModule::* const slots[] = {&JitModule::masks};
@@ -507,6 +519,45 @@ std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why) {
 
 bool jit_check_masks(const Program& P, std::string& why) {
   const std::string src = jit_source_masks(P, why);
+  std::vector<char> code;
+  return !src.empty() && compile(src, code, why);
+}
+
+// The follow path's evaluated form (follow_bits_dev.h): the same table, every group of a thread's tile loaded
+// before the first is evaluated, around follow_eval_bits' body.
+std::string jit_source_follow_bits(const Program& P, std::string& why) {
+  if (!P.follow_mask_ok) { why = "the follow path's evaluated form does not apply: " + P.follow_mask_why; return ""; }
+  // groups of a thread's four loaded before the first evaluation: all four while their 16-B loads (4 VGPRs
+  // each: the key, a column or metadata array of 4 B once, of 8 B twice) stay within 96 VGPRs, which leaves
+  // the kernel four waves per SIMD; else two
+  const MaskProgram& m = P.follow_mask_prog;
+  int loads = 1;
+  for (int c = 0; c < m.ncols; c++)
+    if (m.used >> c & 1) loads += m.coltype[c] == T_I32 ? 1 : 2;
+  loads += ((m.meta & MASK_META_TS) ? 2 : 0) + ((m.meta & MASK_META_OFFSET) ? 2 : 0) +
+           ((m.meta & MASK_META_PARTITION) ? 1 : 0) + ((m.meta & MASK_META_TOPIC) ? 1 : 0);
+  const std::string members = std::string("  static constexpr int AHEAD = ") + (4 * loads * 4 <= 96 ? "4" : "2") +
+                              ";                 // groups loaded before the first evaluation\n";
+  return mask_tab_source(m, members.c_str(),
+                         R"(#include "follow_bits_dev.h"
+extern "C" __global__ __launch_bounds__(kcep::FB_THREADS) void kcep_follow_bits(
+    kcep::MaskArgs A, int k, unsigned long long* __restrict__ bits, unsigned long long* __restrict__ sum, int64_t wpl,
+    int64_t nt, int64_t* __restrict__ tile_starts) {
+  kcep::follow_eval_bits_body(kcep::MaskJitTab{}, A, k, bits, sum, wpl, nt, tile_starts);
+}
+)", why);
+}
+
+std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why) {
+  const std::string src = jit_source_follow_bits(P, why);
+  if (src.empty()) return nullptr;
+  static const char* const names[] = {"kcep_follow_bits"};
+  static hipFunction_t JitModule::* const slots[] = {&JitModule::follow_bits};
+  return build(src, names, slots, 1, why);
+}
+
+bool jit_check_follow_bits(const Program& P, std::string& why) {
+  const std::string src = jit_source_follow_bits(P, why);
   std::vector<char> code;
   return !src.empty() && compile(src, code, why);
 }

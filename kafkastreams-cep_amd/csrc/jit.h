@@ -19,6 +19,7 @@ struct JitModule {
   hipFunction_t nfa_wave = nullptr;     // nfa_wave.h nfa_wave_body, one key per wave (general path)
   hipFunction_t nfa_order = nullptr;    // nfa_dev.h nfa_order_bits_body, the wave kernel's schedule estimate
   hipFunction_t masks = nullptr;        // masks_dev.h masks_body<MaskJitTab>, the mask pre-pass
+  hipFunction_t follow_bits = nullptr;  // follow_bits_dev.h follow_eval_bits_body<MaskJitTab>, the follow path's evaluated form
   ~JitModule();
 };
 
@@ -40,9 +41,15 @@ std::string jit_source_general(const Program& P, std::string& why, bool phases =
 std::shared_ptr<const JitModule> jit_general(const Program& P, std::string& why, bool phases = false, bool stop = false);
 bool jit_check_general(const Program& P, std::string& why);
 
-// the same for the mask pre-pass of a mask-pass eligible pattern (masks_dev.h)
-std::string jit_source_masks(const Program& P, std::string& why);
-std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why);
+// the same for the mask pre-pass of a mask-pass eligible pattern (masks_dev.h); follow: of a pattern in the
+// follow path's evaluated form (Program::follow_mask_prog), which KCEP_FOLLOW_MASK_SPLIT=1 sessions run
+std::string jit_source_masks(const Program& P, std::string& why, bool follow = false);
+std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why, bool follow = false);
 bool jit_check_masks(const Program& P, std::string& why);
+
+// the same for the streaming kernel of the follow path's evaluated form (follow_bits_dev.h)
+std::string jit_source_follow_bits(const Program& P, std::string& why);
+std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why);
+bool jit_check_follow_bits(const Program& P, std::string& why);
 
 }  // namespace kcep

@@ -137,6 +137,16 @@ struct Program {
   std::string follow_why;
   StencilProgram follow{};
   uint32_t follow_next = 0;
+  // evaluated follow form (compile.cpp analyse_follow_mask; sessions with CEP_SESSION_MASK_PASS and a follow
+  // flag): the shape of the follow form, predicates its lowering does not take, every one event-only and
+  // total -- the slots as bytecode for the streaming kernel (follow_bits_dev.h: a times(n) stage's n slots
+  // share one code offset), and the program of k slots and their names the rest of the path reads (its
+  // identity table serves follow_bits over a mask column, KCEP_FOLLOW_MASK_SPLIT=1)
+  bool follow_mask_ok = false;
+  std::string follow_mask_why;
+  StencilProgram follow_mask{};
+  MaskProgram follow_mask_prog{};
+  uint32_t follow_mask_next = 0;
 };
 
 // ---- carried state of the stencil / chain paths (CEP_SESSION_CARRY) ----

@@ -258,6 +258,10 @@ hipError_t follow_carry_rows_launch(const FollowArgs& A, const FollowCarry& C, c
 hipError_t follow_carry_state_launch(const FollowArgs& A, const FollowCarry& C, hipStream_t st);
 int64_t follow_tiles(int64_t n);
 hipError_t follow_bits_launch(const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st);
+// the evaluated form (follow_bits_dev.h): the same planes from the columns the slots read (M; M.mask unused),
+// between the same events; jf: the per-pattern kernel, or null for the built-in one
+hipError_t follow_eval_bits_launch(const MaskArgs& M, const FollowArgs& A, hipEvent_t ev0, hipEvent_t ev1, hipStream_t st,
+                                   hipFunction_t jf);
 hipError_t follow_count_launch(const FollowArgs& A, hipStream_t st);
 hipError_t follow_write_launch(const FollowArgs& A, hipStream_t st);
 hipError_t follow_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int32_t* out,

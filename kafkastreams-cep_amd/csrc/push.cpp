@@ -584,12 +584,31 @@ int push_runs(cep_session* s, const cep_batch* b, hipStream_t st) {
   return CEP_OK;
 }
 
+// The slots' bitmaps of a follow batch, between the session's kernel timing events: follow_bits over the one
+// column the direct form reads; in the evaluated form (M: the columns its predicates read) follow_eval_bits,
+// compiled for the pattern or built in -- or, split (KCEP_FOLLOW_MASK_SPLIT=1), the mask pre-pass into the
+// mask column and follow_bits over that column through the program's identity table.
+static hipError_t follow_planes_launch(cep_session* s, const FollowArgs& A, const MaskArgs& M, hipStream_t st) {
+  hipEvent_t ev0 = s->timing ? s->ev0.e : nullptr, ev1 = s->timing ? s->ev1.e : nullptr;
+  if (!s->follow_eval) return follow_bits_launch(A, ev0, ev1, st);
+  if (!s->follow_split) return follow_eval_bits_launch(M, A, ev0, ev1, st, s->jitm ? s->jitm->follow_bits : nullptr);
+  if (ev0) (void)hipEventRecord(ev0, st);
+  const hipError_t e = masks_launch(M, st, s->jitm ? s->jitm->masks : nullptr);
+  if (e != hipSuccess) return e;
+  FollowArgs B = A;
+  B.val = M.mask;
+  B.topic = nullptr;
+  B.coltype = T_I32;
+  B.use_topic = 0;
+  return follow_bits_launch(B, nullptr, ev1, st);
+}
+
 // A follow carry session's batch (CEP_SESSION_FOLLOW_CARRY, follow.hip "carried walks"): the batch is read in
 // place; its keys' waiting walks are continued once per (segment, slot), the in-batch walks counted with the
 // open ones kept apart; after the one host synchronisation the matches are ordered and written as the runs
 // path's CSR, and the keys' new walk lists appended to the pool.  Nothing of the session's state is written
 // before the key checks are read: a rejected push leaves it as it was.
-static int push_follow_carry(cep_session* s, FollowArgs& A, hipStream_t st) {
+static int push_follow_carry(cep_session* s, FollowArgs& A, const MaskArgs& M, hipStream_t st) {
   const int64_t n = A.n, nt = follow_tiles(n);
   const int K = A.k;
   const int64_t bound = s->rpool_used;            // every walk the pool holds: the carried kernels' launch bound
@@ -644,7 +663,7 @@ static int push_follow_carry(cep_session* s, FollowArgs& A, hipStream_t st) {
   HIPCHECK(runs_carry_build(B, n, s->base, nullptr, nullptr, s->seg.as<int64_t>(), scal, s->rtab.as<int64_t>(),
                             s->rpool.as<int64_t>(), s->rc_a.as<int64_t>(), s->rc_b.as<int64_t>(), ctl + 2,
                             s->scan_tmp.as<int64_t>(), RcExt{}, st, true, max_keys32(s)));
-  HIPCHECK(follow_bits_launch(A, s->timing ? s->ev0.e : nullptr, s->timing ? s->ev1.e : nullptr, st));
+  HIPCHECK(follow_planes_launch(s, A, M, st));
   HIPCHECK(follow_carry_count_launch(A, C, st));
   // the batch's one host synchronisation: the completed and open walks, in-batch and carried, the longest
   // in-batch span, the key-check flags
@@ -696,8 +715,7 @@ static int push_follow_carry(cep_session* s, FollowArgs& A, hipStream_t st) {
 // and compacted in start order, ordered by (completing record, start) as the runs path orders its runs, then
 // written as K-int rows -- from there the batch is a finished stencil batch without carry (cep_collect).
 int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
-  const Program& P = s->pat->prog;
-  const StencilProgram& SP = P.follow;
+  const StencilProgram& SP = *s->sp;               // the pattern's follow form, direct or evaluated
   const int64_t n = b->n;
   NfaArgs in{};
   int rc = stage_inputs(s, b, st, in, true);
@@ -708,16 +726,45 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(s->total.p, 0, 8, st));
     return push_empty(s, st, true);
   }
-  const void* col = b->n_cols ? in.cols[SP.col] : nullptr;
-  const int32_t* topic = SP.use_topic ? in.topic : nullptr;
-  if (SP.use_topic && !topic) {                    // no topic column: every record on topic id 0
-    if (s->h_topic.ensure(size_t(n) * 4)) return fail(CEP_E_HIP, "staging allocation failed");
-    HIPCHECK(hipMemsetAsync(s->h_topic.p, 0, size_t(n) * 4, st));
-    topic = s->h_topic.as<int32_t>();
+  const void* col = nullptr;
+  const int32_t* topic = nullptr;
+  MaskArgs M{};
+  if (s->follow_eval) {
+    // the evaluated form: the columns and metadata its predicates read -- the caller's, group_batch's or
+    // filter_batch's, with their stream positions (a default ts / offset is the position)
+    const MaskProgram& MP = s->pat->prog.follow_mask_prog;
+    M.P = s->mprog.as<MaskProgram>();
+    M.key = in.key;
+    M.topic = (MP.meta & MASK_META_TOPIC) ? in.topic : nullptr;
+    M.partition = (MP.meta & MASK_META_PARTITION) ? in.partition : nullptr;
+    M.offset = (MP.meta & MASK_META_OFFSET) ? in.offset : nullptr;
+    M.ts = (MP.meta & MASK_META_TS) ? in.ts : nullptr;
+    M.pos = s->cur_pos;
+    M.n = n;
+    M.base = s->carry ? s->base : 0;
+    M.mask = s->follow_split ? s->mcol.as<int32_t>() : nullptr;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(M.key) | reinterpret_cast<uintptr_t>(M.topic) |
+                     reinterpret_cast<uintptr_t>(M.partition) | reinterpret_cast<uintptr_t>(M.offset) |
+                     reinterpret_cast<uintptr_t>(M.ts) | reinterpret_cast<uintptr_t>(M.pos);
+    for (int c = 0; c < b->n_cols && c < 16; c++)
+      if (MP.used >> c & 1) {
+        M.cols[c] = in.cols[c];
+        bits |= reinterpret_cast<uintptr_t>(M.cols[c]);
+      }
+    if (bits & 15) return fail(CEP_E_ARG, "device columns must be 16-byte aligned");
+    if (s->follow_split && size_t(n) * 4 > s->mcol.cap) return fail(CEP_E_ARG, "batch larger than the session capacity");
+  } else {
+    col = b->n_cols ? in.cols[SP.col] : nullptr;
+    topic = SP.use_topic ? in.topic : nullptr;
+    if (SP.use_topic && !topic) {                  // no topic column: every record on topic id 0
+      if (s->h_topic.ensure(size_t(n) * 4)) return fail(CEP_E_HIP, "staging allocation failed");
+      HIPCHECK(hipMemsetAsync(s->h_topic.p, 0, size_t(n) * 4, st));
+      topic = s->h_topic.as<int32_t>();
+    }
+    if (!col) return fail(CEP_E_ARG, "null value column");
+    if ((reinterpret_cast<uintptr_t>(in.key) | reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(topic)) & 15)
+      return fail(CEP_E_ARG, "device columns must be 16-byte aligned");
   }
-  if (!col) return fail(CEP_E_ARG, "null value column");
-  if ((reinterpret_cast<uintptr_t>(in.key) | reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(topic)) & 15)
-    return fail(CEP_E_ARG, "device columns must be 16-byte aligned");
   const int64_t nt = follow_tiles(n);
   if (size_t(nt) * 64 * size_t(SP.k + 1) * 8 > s->fw_bits.cap) return fail(CEP_E_ARG, "batch larger than the session capacity");
   if (s->scan_tmp.ensure(size_t(nt / 16 + 4) * 8)) return fail(CEP_E_HIP, "allocation failed");
@@ -725,7 +772,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   FollowArgs A{};
   A.key = in.key; A.val = col; A.topic = topic; A.n = n;
   A.prog_dev = s->prog.as<StencilProgram>();
-  A.k = SP.k; A.coltype = SP.coltype; A.use_topic = SP.use_topic; A.next_mask = P.follow_next;
+  A.k = SP.k; A.coltype = SP.coltype; A.use_topic = SP.use_topic; A.next_mask = s->follow_next;
   A.bits = s->fw_bits.as<unsigned long long>();
   A.sum = s->fw_sum.as<unsigned long long>();
   A.tile_starts = s->fw_tile.as<int64_t>();
@@ -734,8 +781,8 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   A.scan_tmp = s->scan_tmp.as<int64_t>();
   A.nm = scal + 4;
   A.max_span = reinterpret_cast<unsigned long long*>(scal + 5);
-  if (s->carry) return push_follow_carry(s, A, st);
-  HIPCHECK(follow_bits_launch(A, s->timing ? s->ev0.e : nullptr, s->timing ? s->ev1.e : nullptr, st));
+  if (s->carry) return push_follow_carry(s, A, M, st);
+  HIPCHECK(follow_planes_launch(s, A, M, st));
   HIPCHECK(follow_count_launch(A, st));
   // the batch's one host synchronisation: the completed walks and their longest span
   int64_t h[2] = {0, 0};

@@ -109,6 +109,11 @@ struct cep_session {
   // lowering, or on a CEP_SESSION_MASK_PASS session of an eligible pattern its mask-pass form
   const kcep::StencilProgram* sp = nullptr;
   bool mask_pass = false;       // stencil / chain batches run the pre-pass (masks.hip) first
+  // a follow session in the evaluated form (Program::follow_mask_ok, CEP_SESSION_MASK_PASS with a follow flag):
+  // sp = &follow_mask, the bitmaps come from follow_eval_bits over the columns the predicates read (mprog);
+  // follow_split (KCEP_FOLLOW_MASK_SPLIT=1 at open): from the pre-pass into mcol and follow_bits over it
+  bool follow_eval = false, follow_split = false;
+  uint32_t follow_next = 0;     // a follow session's skip-till-next slots
   int last_path = 0;            // path of the last batch
   int device = 0;
   hipStream_t stream = nullptr;
@@ -183,7 +188,7 @@ struct cep_session {
   // kernels compiled for the pattern (jit.cpp); null: the built-in interpreting kernels run
   bool jit_on = false;                     // allowed (not CEP_SESSION_INTERPRET / KCEP_JIT=0)
   std::shared_ptr<const JitModule> jit;    // runs path
-  std::shared_ptr<const JitModule> jitm;   // mask pass: the pre-pass kernel
+  std::shared_ptr<const JitModule> jitm;   // mask pass: the pre-pass kernel; evaluated follow form: its streaming kernel
   std::shared_ptr<const JitModule> jitg;   // general path (built at open, or at the first general batch)
   bool jitg_tried = false;
   std::shared_ptr<const JitModule> jitg_stop;   // its CEP_BATCH_STOP_AT_ERROR build (at the first flagged batch)
@@ -271,7 +276,7 @@ constexpr size_t kZeroCopyMax = size_t(1) << 20;
 // (walks of k words)
 inline bool walk_session(const cep_session* s) { return s->carry && s->path == CEP_PATH_FOLLOW; }
 inline int tail_rw(const cep_session* s) {
-  return walk_session(s) ? s->pat->prog.follow.k : 5 + int(s->pat->prog.coltypes.size());
+  return walk_session(s) ? s->sp->k : 5 + int(s->pat->prog.coltypes.size());
 }
 inline bool tail_session(const cep_session* s) { return s->carry && (s->path == CEP_PATH_RUNS || s->path == CEP_PATH_FOLLOW); }
 // the last batch left the general / runs CSR on the device (o_record ...; its match count in scal[3])

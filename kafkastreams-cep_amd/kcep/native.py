@@ -86,7 +86,8 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_match_count_to", "cep_state_evict", "cep_state_import_keys", "cep_state_positions",
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
            "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped",
-           "cep_filter_tile_records", "cep_pattern_mask_pass", "cep_pattern_follow", "cep_follow_tile_records"]
+           "cep_filter_tile_records", "cep_pattern_mask_pass", "cep_pattern_follow", "cep_follow_tile_records",
+           "cep_pattern_follow_mask"]
 
 _lib = None
 
@@ -155,6 +156,8 @@ def lib():
         L.cep_pattern_follow.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
         L.cep_follow_tile_records.argtypes = []
         L.cep_follow_tile_records.restype = C.c_int32
+    if hasattr(L, "cep_pattern_follow_mask"):   # (KCEP_LIB A/B runs may load an older build)
+        L.cep_pattern_follow_mask.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -260,6 +263,19 @@ class CompiledPattern:
             return True, k.value, nxt.value, ""
         return False, 0, 0, lib().cep_last_error().decode()
 
+    @property
+    def follow_mask(self):
+        """cep_pattern_follow_mask: ``(ok, k, next_mask, why)`` -- whether a session with ``mask_pass=True`` and
+        ``follow=True`` / ``follow_carry=True`` runs the pattern on the follow path in its evaluated form (the
+        shape of ``follow``, predicates over several columns, arithmetic or metadata, each total and
+        event-only), its slots, the mask of the skip-till-next slots, and the reason when it does not (a
+        pattern ``follow`` takes is not eligible: it keeps the direct form)."""
+        k, nxt = C.c_int32(), C.c_uint32()
+        rc = lib().cep_pattern_follow_mask(self.h, C.byref(k), C.byref(nxt))
+        if rc == CEP_OK:
+            return True, k.value, nxt.value, ""
+        return False, 0, 0, lib().cep_last_error().decode()
+
     def kernel_source(self, path=PATH_RUNS) -> str:
         """HIP source of the kernels compiled for this pattern (cep_pattern_kernel_source)."""
         n = C.c_size_t()
@@ -304,7 +320,12 @@ class Session:
         (``CompiledPattern.follow``) opens on the follow path instead of the general NFA; no effect on any
         other pattern, nor with ``carry=True``.
         ``follow_carry=True`` (CEP_SESSION_FOLLOW_CARRY): the same with ``carry=True`` too -- the session
-        carries every key's waiting walks ("KCSW" state blobs), batches follow the runs carry rules."""
+        carries every key's waiting walks ("KCSW" state blobs), batches follow the runs carry rules.
+        ``mask_pass=True`` together with ``follow=True`` or ``follow_carry=True``: the follow path also takes,
+        in its evaluated form, a pattern of that shape whose predicates read several columns, arithmetic or
+        event metadata (``CompiledPattern.follow_mask``): its streaming kernel evaluates them into the
+        bitmaps, compiled for the pattern unless ``interpret=True``.  With one of the two alone such a pattern
+        opens where it always did."""
         self.pattern = pattern
         self.h = C.c_void_p()
         # lane_nfa: None = the library's choice, True = one key per lane, False = one key per wave

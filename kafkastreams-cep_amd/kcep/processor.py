@@ -132,7 +132,9 @@ class GpuCEPProcessor:
         self.mask_pass = bool(mask_pass)
         # CEP_SESSION_FOLLOW_CARRY for the session init() opens: an eligible pattern of strict and
         # skip-till-next stages then runs on the follow path (native.CompiledPattern.follow), which takes
-        # batches as the runs path does; no effect on other patterns
+        # batches as the runs path does; no effect on other patterns.  With mask_pass too, the path also
+        # takes such a pattern whose predicates read several columns, arithmetic or event metadata, in its
+        # evaluated form (native.CompiledPattern.follow_mask)
         self.follow = bool(follow)
         self.device = device
         self.mode = mode
