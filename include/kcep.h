@@ -64,7 +64,9 @@ extern "C" {
 #define CEP_PATH_FOLLOW 5         /* strict and skip-till-next (followedBy) stages of cardinality ONE / times(n):
                                      one deterministic walk per start record over per-slot bitmaps
                                      (CEP_SESSION_FOLLOW, cep_pattern_follow); sessions without carry, and
-                                     with CEP_SESSION_FOLLOW_CARRY carry sessions (waiting walks carried per key) */
+                                     with CEP_SESSION_FOLLOW_CARRY carry sessions (waiting walks carried per key);
+                                     with CEP_SESSION_FOLLOW_MANY also oneOrMore stages between the first and
+                                     the last (cep_pattern_follow_many; variable-length matches) */
 
 typedef struct cep_pattern cep_pattern;
 typedef struct cep_session cep_session;
@@ -246,6 +248,37 @@ typedef struct {
                                     arrays the predicates read must be 16-byte aligned.  The flag does nothing
                                     for a pattern that is not eligible. */
 
+#define CEP_SESSION_FOLLOW_MANY 256 /* opt-in: the follow path also for patterns with oneOrMore stages, such as
+                                    A followedBy B+ followedBy C.  Implies CEP_SESSION_FOLLOW.  A pattern is
+                                    eligible (cep_pattern_follow_many) iff it has the shape CEP_SESSION_FOLLOW
+                                    asks for with oneOrMore allowed on, and present on at least one of, the
+                                    stages that are neither first nor last -- no times on such a stage, no
+                                    zeroOrMore / optional, no folds, distinct names, strict first stage of
+                                    cardinality ONE, at most 8 slots (a oneOrMore stage is one slot), at least
+                                    one skip-till-next stage (an all-strict pattern keeps the runs path) -- and
+                                    every oneOrMore stage's predicate, with its topic filter, provably excludes
+                                    its successor's (the rule of CEP_PATH_RUNS).  Then no run branches in any
+                                    way the output shows: a walk that has taken a oneOrMore slot B at record r
+                                    scans the key's records after r -- a B record is collected as one more B
+                                    entry, the first record of the next slot is taken, a record that is neither
+                                    is passed over if B or the next slot is skip-till-next and kills the walk if
+                                    both are strict.  Matches have variable length and come as the runs path's
+                                    CSR with batch indices as positions, by (completing record, start), entries
+                                    final slot first, a oneOrMore slot's collected records (descending) before
+                                    the slot's first record, all under the stage's name; cep_matches.path =
+                                    CEP_PATH_FOLLOW, and cep_device_match_count reads the count where runs
+                                    batches keep it.  2^31 entries or more in one batch: CEP_E_RUN_CAPACITY.
+                                    The predicates lower as for CEP_SESSION_FOLLOW; a pattern that needs the
+                                    evaluated form (*evaluated = 1) opens on the path only with
+                                    CEP_SESSION_MASK_PASS also set.  With the flag such a pattern opens on
+                                    CEP_PATH_FOLLOW before runs / general, and force_path = CEP_PATH_FOLLOW
+                                    succeeds for it only with the flag.  Batch rules are those of a follow
+                                    session without carry.  Sessions without CEP_SESSION_CARRY only (a carried
+                                    walk through a oneOrMore slot is not k words): with CEP_SESSION_CARRY the
+                                    flag does nothing and force_path = CEP_PATH_FOLLOW fails with
+                                    CEP_E_UNSUPPORTED.  The flag does nothing for a pattern that is not
+                                    eligible, and every other pattern and flag behaves as without it. */
+
 #define CEP_MEM_HOST 0
 #define CEP_MEM_DEVICE 1
 
@@ -395,6 +428,14 @@ int cep_pattern_follow(const cep_pattern* p, int32_t* k, uint32_t* next_mask);
  * else CEP_E_UNSUPPORTED with the reason in cep_last_error (a pattern cep_pattern_follow takes is not eligible:
  * it keeps the direct form).  Host-only. */
 int cep_pattern_follow_mask(const cep_pattern* p, int32_t* k, uint32_t* next_mask);
+/* CEP_OK if the pattern takes the follow path with oneOrMore stages (CEP_SESSION_FOLLOW_MANY): *k = its slots (a
+ * oneOrMore stage is one), *next_mask as for cep_pattern_follow, bit s of *many_mask = slot s is a oneOrMore
+ * stage, *evaluated = 0 if the direct lowering takes every predicate, 1 if the pattern needs the evaluated form
+ * (then the session also needs CEP_SESSION_MASK_PASS); the outputs may be NULL.  Else CEP_E_UNSUPPORTED with the
+ * reason in cep_last_error (a pattern without a oneOrMore stage is not eligible: cep_pattern_follow answers for
+ * it).  Host-only. */
+int cep_pattern_follow_many(const cep_pattern* p, int32_t* k, uint32_t* next_mask, uint32_t* many_mask,
+                            int32_t* evaluated);
 
 /* --- session: one per stream task (CEPProcessor.init :88-108) --- */
 int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** out);

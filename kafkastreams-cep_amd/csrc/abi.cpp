@@ -13,7 +13,8 @@
 //   stencil  (stencil.hip)  strict single-cardinality patterns, SURVEY Q9
 //   runs     (runs.hip)     deterministic strict runs
 //   follow   (follow.hip)   strict and skip-till-next stages: one deterministic walk per start (opt-in;
-//                           carry sessions carry the waiting walks per key)
+//                           carry sessions carry the waiting walks per key; with CEP_SESSION_FOLLOW_MANY
+//                           oneOrMore stages too, their matches of variable length)
 //   general  (nfa.hip)      every pattern the IR expresses: one lane (or wave) per key
 //                           running the reference NFA over an HBM arena
 #include <dlfcn.h>
@@ -121,7 +122,10 @@ int cep_pattern_check(const cep_pattern* p, int32_t session_flags) {
   // a carry session keeps its keys' full NFA state on the general path whenever a batch needs it
   if ((session_flags & CEP_SESSION_CARRY) && !P.general_ok)
     return fail(CEP_E_UNSUPPORTED, "pattern cannot be lowered to the device NFA: " + P.general_why);
-  if (!P.stencil_ok && !P.runs_ok && !P.general_ok)
+  // (CEP_SESSION_FOLLOW_MANY: a pattern with oneOrMore stages the follow path takes, as cep_session_open decides)
+  const bool many = (session_flags & CEP_SESSION_FOLLOW_MANY) && !(session_flags & CEP_SESSION_CARRY) && P.follow_many_ok &&
+                    (!P.follow_many_eval || (session_flags & CEP_SESSION_MASK_PASS));
+  if (!P.stencil_ok && !P.runs_ok && !P.general_ok && !many)
     return fail(CEP_E_UNSUPPORTED, "no device path: " + P.general_why);
   return CEP_OK;
 }
@@ -159,10 +163,22 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   // ... with CEP_SESSION_MASK_PASS also a pattern of the follow shape whose predicates the direct lowering does
   // not take (cep_pattern_follow_mask), in the evaluated form
   const bool follow_eval = (opts->flags & CEP_SESSION_MASK_PASS) && P.follow_mask_ok;
+  // CEP_SESSION_FOLLOW_MANY: a pattern with oneOrMore stages (cep_pattern_follow_many), on sessions without
+  // carry; implies CEP_SESSION_FOLLOW; the evaluated form again only with CEP_SESSION_MASK_PASS
+  const bool many_flag = (opts->flags & CEP_SESSION_FOLLOW_MANY) != 0;
   const bool follow_flag =
-      (((opts->flags & CEP_SESSION_FOLLOW) && !carry) || follow_carry) && (P.follow_ok || follow_eval);
-  if (path == 0) path = sp ? fast : follow_flag ? CEP_PATH_FOLLOW : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
-  if (path == CEP_PATH_FOLLOW && !P.follow_ok && !follow_eval)
+      (((opts->flags & (CEP_SESSION_FOLLOW | CEP_SESSION_FOLLOW_MANY)) && !carry) || follow_carry) && (P.follow_ok || follow_eval);
+  const bool follow_many =
+      many_flag && !carry && P.follow_many_ok && (!P.follow_many_eval || (opts->flags & CEP_SESSION_MASK_PASS));
+  if (path == 0)
+    path = sp ? fast : follow_flag || follow_many ? CEP_PATH_FOLLOW : P.runs_ok ? CEP_PATH_RUNS : CEP_PATH_GENERAL;
+  if (path == CEP_PATH_FOLLOW && many_flag && P.follow_many_ok && !follow_many)
+    return fail(CEP_E_UNSUPPORTED,
+                carry ? "follow path does not apply: CEP_SESSION_FOLLOW_MANY takes sessions without CEP_SESSION_CARRY "
+                        "(a carried oneOrMore walk is not K words)"
+                      : "follow path does not apply: CEP_SESSION_FOLLOW_MANY takes the pattern in the evaluated form, "
+                        "which needs CEP_SESSION_MASK_PASS");
+  if (path == CEP_PATH_FOLLOW && !P.follow_ok && !follow_eval && !follow_many)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: " + P.follow_why);
   if (path == CEP_PATH_FOLLOW && carry && !follow_carry)
     return fail(CEP_E_UNSUPPORTED, "follow path does not apply: it takes sessions without CEP_SESSION_CARRY");
@@ -187,11 +203,14 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->pat = p;
   s->opts = *opts;
   s->path = path;
-  s->follow_eval = follow && !P.follow_ok;          // (a pattern the direct lowering takes keeps it)
-  s->follow_split = s->follow_eval && getenv_flag("KCEP_FOLLOW_MASK_SPLIT");
-  s->follow_next = s->follow_eval ? P.follow_mask_next : P.follow_next;
+  // (a pattern with oneOrMore stages has neither of the other follow forms)
+  s->follow_many = follow && follow_many;
+  s->follow_many_mask = s->follow_many ? P.follow_many_mask : 0;
+  s->follow_eval = follow && (s->follow_many ? P.follow_many_eval : !P.follow_ok);   // (a pattern the direct lowering takes keeps it)
+  s->follow_split = s->follow_eval && !s->follow_many && getenv_flag("KCEP_FOLLOW_MASK_SPLIT");
+  s->follow_next = s->follow_many ? P.follow_many_next : s->follow_eval ? P.follow_mask_next : P.follow_next;
   // (never null: a collect before any push reads its k)
-  s->sp = follow ? (s->follow_eval ? &P.follow_mask : &P.follow) : sp ? sp : &P.stencil;
+  s->sp = follow ? (s->follow_many ? &P.follow_many : s->follow_eval ? &P.follow_mask : &P.follow) : sp ? sp : &P.stencil;
   s->mask_pass = masked && (path == CEP_PATH_STENCIL || path == CEP_PATH_CHAIN);
   s->device = opts->device;
   auto cleanup = [&](int rc) {
@@ -207,7 +226,10 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
     const StencilProgram& FP = *s->sp;
     const size_t nt = size_t(follow_tiles(cap)), planes = size_t(FP.k) + 1;
     if (s->prog.ensure(sizeof(StencilProgram)) || s->total.ensure(64) || s->sum.ensure(64) ||
-        (!carry && s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap))) || s->fw_bits.ensure(planes * nt * 64 * 8) ||
+        (!carry && !s->follow_many && s->out.ensure(sizeof(int32_t) * size_t(FP.k) * size_t(cap))) ||
+        // (a session of a pattern with oneOrMore stages writes the CSR too, and sums the walks' lengths per word)
+        (s->follow_many && (s->fw_len.ensure(nt * 64 * 8) || s->fw_lpre.ensure(nt * 64 * 8))) ||
+        s->fw_bits.ensure(planes * nt * 64 * 8) ||
         s->fw_sum.ensure(planes * nt * 8) || s->fw_tile.ensure(nt * 8) || s->fw_cnt.ensure(nt * 64 * 8) ||
         s->fw_pre.ensure(nt * 64 * 8) || s->scan_tmp.ensure((nt / 16 + 4) * 8) ||
         // (a carry session writes the runs path's CSR instead of rows, and keeps the open starts apart)
@@ -220,7 +242,8 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
     if (s->follow_eval &&
         (s->mprog.ensure(sizeof(MaskProgram)) ||
          (s->follow_split && s->mcol.ensure(sizeof(int32_t) * size_t((cap + 3) & ~int64_t(3)))) ||
-         hipMemcpy(s->mprog.p, &P.follow_mask_prog, sizeof(MaskProgram), hipMemcpyHostToDevice)))
+         hipMemcpy(s->mprog.p, s->follow_many ? &P.follow_many_prog : &P.follow_mask_prog, sizeof(MaskProgram),
+                   hipMemcpyHostToDevice)))
       return cleanup(fail(CEP_E_HIP, "device allocation failed"));
   }
   if (sp && path != CEP_PATH_GENERAL && !follow) {
@@ -293,7 +316,8 @@ int cep_session_open(const cep_pattern* p, const cep_opts* opts, cep_session** o
   s->jit_on = !(opts->flags & CEP_SESSION_INTERPRET) && !(env_jit && !strcmp(env_jit, "0"));
   if (s->jit_on && path == CEP_PATH_RUNS) s->jit = jit_runs(P, s->jit_why);   // on failure: built-in kernels
   if (s->jit_on && s->mask_pass) s->jitm = jit_masks(P, s->jit_why);        // on failure: the built-in kernel
-  if (s->jit_on && s->follow_eval) s->jitm = s->follow_split ? jit_masks(P, s->jit_why, true) : jit_follow_bits(P, s->jit_why);
+  if (s->jit_on && s->follow_eval)
+    s->jitm = s->follow_split ? jit_masks(P, s->jit_why, true) : jit_follow_bits(P, s->jit_why, s->follow_many);
   if (s->jit_on && path == CEP_PATH_GENERAL) {
     s->jitg = jit_general(P, s->jit_why, s->opts.flags & CEP_SESSION_PROFILE);
     s->jitg_tried = true;
@@ -400,14 +424,26 @@ int cep_pattern_follow_mask(const cep_pattern* p, int32_t* k, uint32_t* next_mas
   return CEP_OK;
 }
 
+int cep_pattern_follow_many(const cep_pattern* p, int32_t* k, uint32_t* next_mask, uint32_t* many_mask, int32_t* evaluated) {
+  if (!p) return fail(CEP_E_ARG, "null argument");
+  const Program& P = p->prog;
+  if (!P.follow_many_ok) return fail(CEP_E_UNSUPPORTED, "follow path with oneOrMore stages does not apply: " + P.follow_many_why);
+  if (k) *k = P.follow_many.k;
+  if (next_mask) *next_mask = P.follow_many_next;
+  if (many_mask) *many_mask = P.follow_many_mask;
+  if (evaluated) *evaluated = P.follow_many_eval ? 1 : 0;
+  return CEP_OK;
+}
+
 int cep_pattern_kernel_source(const cep_pattern* p, int path, char* buf, size_t cap, size_t* needed) {
   if (!p || !needed) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
   const bool masks = mask_pass_path(p->prog, path);
-  const bool fbits = path == CEP_PATH_FOLLOW && p->prog.follow_mask_ok;   // the follow path's evaluated form
+  const bool fmany = p->prog.follow_many_ok && p->prog.follow_many_eval;   // ... with oneOrMore stages
+  const bool fbits = path == CEP_PATH_FOLLOW && (p->prog.follow_mask_ok || fmany);   // the follow path's evaluated form
   if (!runs && !general && !masks && !fbits) return no_kernels(p->prog, path);
   std::string why;
-  const std::string src = fbits   ? jit_source_follow_bits(p->prog, why)
+  const std::string src = fbits   ? jit_source_follow_bits(p->prog, why, fmany)
                           : masks ? jit_source_masks(p->prog, why)
                           : runs  ? jit_source_runs(p->prog, why)
                                   : jit_source_general(p->prog, why);
@@ -423,7 +459,7 @@ int cep_pattern_build_kernels(const cep_pattern* p, int path) {
   if (!p) return fail(CEP_E_ARG, "null argument");
   const bool runs = path == CEP_PATH_RUNS && p->prog.runs_ok, general = path == CEP_PATH_GENERAL && p->prog.general_ok;
   const bool masks = mask_pass_path(p->prog, path);
-  const bool fbits = path == CEP_PATH_FOLLOW && p->prog.follow_mask_ok;
+  const bool fbits = path == CEP_PATH_FOLLOW && (p->prog.follow_mask_ok || (p->prog.follow_many_ok && p->prog.follow_many_eval));
   if (!runs && !general && !masks && !fbits) return no_kernels(p->prog, path);
   std::string why;
   if (!(fbits   ? jit_check_follow_bits(p->prog, why)

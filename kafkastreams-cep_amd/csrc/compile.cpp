@@ -616,14 +616,23 @@ void analyse_runs(Program& P) {
 // lowered as analyse_stencil lowers stages; bit s of follow_next: slot s is skip-till-next.
 // the shape both forms of the path take (analyse_follow, analyse_follow_mask): K = the slots, bit s of next:
 // slot s is skip-till-next
-bool follow_shape(const Program& P, int& K, uint32_t& next, std::string& why) {
+// many (CEP_SESSION_FOLLOW_MANY, analyse_follow_many): null, or receives bit s: slot s is a oneOrMore stage --
+// then such stages are taken where they are neither first nor last, at least one is asked for, and each one's
+// predicate has to exclude its successor's (TAKE and PROCEED never match one record: no branch run)
+bool follow_shape(const Program& P, int& K, uint32_t& next, std::string& why, uint32_t* many = nullptr) {
   auto no = [&](const std::string& w) { why = w; return false; };
   const int np = int(P.pats.size());
   K = 0;
   next = 0;
+  if (many) *many = 0;
   for (int i = 0; i < np; i++) {
     const auto& p = P.pats[i];
-    if (p.one_or_more) return no(p.optional ? "zeroOrMore stage" : "oneOrMore stage");
+    if (p.one_or_more) {
+      if (!many || p.optional) return no(p.optional ? "zeroOrMore stage" : "oneOrMore stage");
+      if (i == 0) return no("oneOrMore on the first stage");
+      if (i == np - 1) return no("oneOrMore on the last stage");
+      if (p.times > 1) return no("times together with oneOrMore");
+    }
     if (p.optional) return no("optional stage");
     if (!p.folds.empty()) return no("fold");
     for (int j = 0; j < i; j++)
@@ -634,27 +643,30 @@ bool follow_shape(const Program& P, int& K, uint32_t& next, std::string& why) {
     if (i == 0 && p.times > 1) return no("times on the first stage");
     if (p.times < 1) return no("times below 1");
     if (K + p.times > STENCIL_MAX_K) return no("more than 8 slots (stages, a times(n) stage counting n)");
+    if (p.one_or_more) *many |= 1u << K;
     for (int r = 0; r < p.times; r++, K++)
       if (p.strategy == S_NEXT) next |= 1u << K;
   }
+  if (many && !*many) return no("no oneOrMore stage: cep_pattern_follow answers for the pattern");
   if (!next)
     return no(std::string("no skip-till-next stage: ") + (P.stencil_ok ? "the stencil path takes the pattern"
                                                           : P.runs_ok  ? "the runs path takes the pattern"
                                                                        : "the pattern keeps its path"));
+  if (many)
+    for (int i = 1; i + 1 < np; i++) {
+      if (!P.pats[i].one_or_more) continue;
+      const auto &p = P.pats[i], &q = P.pats[i + 1];
+      ExprP pw = p.topic >= 0 ? mk(OP_AND, mk_topic(p.topic), p.pred) : p.pred;
+      ExprP qw = q.topic >= 0 ? mk(OP_AND, mk_topic(q.topic), q.pred) : q.pred;
+      if (!disjoint(pw, qw)) return no("oneOrMore predicate not provably exclusive of its successor's");
+    }
   return true;
 }
 
-void analyse_follow(Program& P) {
-  auto no = [&](const std::string& w) { P.follow_ok = false; P.follow_why = w; };
-  StencilProgram& S = P.follow;
+// the slots of a follow shape lowered directly (one column's intervals, a table); false + why
+bool lower_follow_direct(const Program& P, int K, StencilProgram& S, std::string& why) {
   memset(&S, 0, sizeof S);
-  P.follow_next = 0;
   const int np = int(P.pats.size());
-  int K = 0;
-  {
-    std::string why;
-    if (!follow_shape(P, K, P.follow_next, why)) return no(why);
-  }
   Lowering L;
   S.k = K;
   for (int i = 0, slot = 0; i < np && L.ok; i++) {
@@ -667,11 +679,22 @@ void analyse_follow(Program& P) {
       put_slot(S, slot, d);
     }
   }
-  if (!L.ok) return no(L.why);
+  if (!L.ok) { why = L.why; return false; }
   if (L.col < 0) { L.col = 0; L.coltype = P.coltypes.empty() ? T_I32 : P.coltypes[0]; }
   S.col = L.col;
   S.coltype = L.coltype;
-  if (!build_table(S)) return no("predicates cut the value axis into more than 16 intervals");
+  if (!build_table(S)) { why = "predicates cut the value axis into more than 16 intervals"; return false; }
+  return true;
+}
+
+void analyse_follow(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_ok = false; P.follow_why = w; };
+  memset(&P.follow, 0, sizeof P.follow);
+  P.follow_next = 0;
+  int K = 0;
+  std::string why;
+  if (!follow_shape(P, K, P.follow_next, why)) return no(why);
+  if (!lower_follow_direct(P, K, P.follow, why)) return no(why);
   P.follow_ok = true;
   P.follow_why.clear();
 }
@@ -908,19 +931,12 @@ void analyse_mask_pass(Program& P) {
 // predicates its lowering does not take, every stage predicate event-only and total (the rule of
 // analyse_mask_pass: the streaming kernel evaluates a slot on every record).  The n slots of a times(n)
 // stage share one code offset.
-void analyse_follow_mask(Program& P) {
-  auto no = [&](const std::string& w) { P.follow_mask_ok = false; P.follow_mask_why = w; };
-  StencilProgram& S = P.follow_mask;
-  MaskProgram& M = P.follow_mask_prog;
+// the slots of a follow shape as bytecode for the streaming kernel, and the program of K slots and their names
+// the rest of the path reads; false + why
+bool lower_follow_eval(const Program& P, int K, StencilProgram& S, MaskProgram& M, std::string& why) {
+  auto no = [&](const std::string& w) { why = w; return false; };
   memset(&S, 0, sizeof S);
   memset(&M, 0, sizeof M);
-  P.follow_mask_next = 0;
-  int K = 0;
-  {
-    std::string why;
-    if (!follow_shape(P, K, P.follow_mask_next, why)) return no(why);
-  }
-  if (P.follow_ok) return no("the pattern lowers to the follow path directly");
   if (P.coltypes.size() > 16) return no("too many columns");
   static_assert(MASK_SLOTS == STENCIL_MAX_K, "a slot of the follow path is a slot of the mask program");
   CodeGen cg;
@@ -954,8 +970,46 @@ void analyse_follow_mask(Program& P) {
   S.lut_lo = 0;
   S.lut_n = 256;
   for (int m = 0; m < 256; m++) S.lut[1 + m] = uint8_t(m);
+  return true;
+}
+
+void analyse_follow_mask(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_mask_ok = false; P.follow_mask_why = w; };
+  memset(&P.follow_mask, 0, sizeof P.follow_mask);
+  memset(&P.follow_mask_prog, 0, sizeof P.follow_mask_prog);
+  P.follow_mask_next = 0;
+  int K = 0;
+  std::string why;
+  if (!follow_shape(P, K, P.follow_mask_next, why)) return no(why);
+  if (P.follow_ok) return no("the pattern lowers to the follow path directly");
+  if (!lower_follow_eval(P, K, P.follow_mask, P.follow_mask_prog, why)) return no(why);
   P.follow_mask_ok = true;
   P.follow_mask_why.clear();
+}
+
+// The follow form with oneOrMore stages (kcep_internal.h Program::follow_many_ok; CEP_SESSION_FOLLOW_MANY): a
+// oneOrMore stage is one slot flagged many.  Its edges are TAKE(B), IGNORE(NOT B) if it is skip-till-next and
+// PROCEED(C OR NOT B) / PROCEED(C) if it is strict / skip-till-next (build_stages above); with B AND C
+// unsatisfiable TAKE and PROCEED never match one record, and IGNORE and PROCEED match together only on a C
+// record, where PROCEED succeeds without a branch run -- every run stays one deterministic walk that collects
+// the B records between the stage's first and its successor's.  The direct lowering where it takes every
+// predicate, else the evaluated form under analyse_follow_mask's rule.
+void analyse_follow_many(Program& P) {
+  auto no = [&](const std::string& w) { P.follow_many_ok = false; P.follow_many_why = w; };
+  memset(&P.follow_many, 0, sizeof P.follow_many);
+  memset(&P.follow_many_prog, 0, sizeof P.follow_many_prog);
+  P.follow_many_next = P.follow_many_mask = 0;
+  P.follow_many_eval = false;
+  int K = 0;
+  std::string why, why_eval;
+  if (!follow_shape(P, K, P.follow_many_next, why, &P.follow_many_mask)) return no(why);
+  if (!lower_follow_direct(P, K, P.follow_many, why)) {
+    if (!lower_follow_eval(P, K, P.follow_many, P.follow_many_prog, why_eval))
+      return no(why + "; the evaluated form does not apply: " + why_eval);
+    P.follow_many_eval = true;
+  }
+  P.follow_many_ok = true;
+  P.follow_many_why.clear();
 }
 
 }  // namespace
@@ -1103,6 +1157,7 @@ int compile_ir(const uint8_t* ir, size_t len, Program& P, std::string& err) {
   analyse_mask_pass(P);
   analyse_follow(P);
   analyse_follow_mask(P);
+  analyse_follow_many(P);
   P.has_seq = false;
   for (const auto& pd : P.pats) {
     P.has_seq = P.has_seq || uses_seq(pd.pred);

@@ -22,6 +22,9 @@
 // A strict hop is one bit test; a skip-till-next hop and the end of the start's key segment are a
 // find-next-set-bit: the rest of the current word, then second-level words, then one first-level word,
 // <= 2 + gap / 4096 word reads.
+// With oneOrMore stages (CEP_SESSION_FOLLOW_MANY, compile.cpp analyse_follow_many; sessions without carry) a
+// match has a variable length: follow_many_walks count and write, follow_many_len and follow_many_rows leave
+// the runs path's CSR instead of rows ("oneOrMore slots" below).
 #include "follow_bits_dev.h"
 #include "stencil_kernel.h"
 
@@ -378,6 +381,263 @@ hipError_t follow_write_launch(const FollowArgs& A, hipStream_t st) {
 hipError_t follow_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int32_t* out,
                               int64_t* total, hipStream_t st) {
   hipLaunchKernelGGL(follow_rows, dim3(blocks256(nm)), dim3(256), 0, st, follow_maps(A), sorted, nm, out, total);
+  return hipGetLastError();
+}
+
+// ---- oneOrMore slots (CEP_SESSION_FOLLOW_MANY): variable-length matches ----
+// A oneOrMore stage is one slot flagged many (compile.cpp analyse_follow_many): its predicate excludes its
+// successor's.  The hop out of a many slot B at record r into slot s scans the key's records after r: a B
+// record is collected, the first slot-s record is taken, a record that is neither is skipped if B or s is
+// skip-till-next and kills the walk if both are strict.  So the mixed hop is the find-next-set on plane s
+// the other hops take, and the strict / strict hop a find-next-zero on plane B (word by word over inverted
+// words: a second level says nothing about all-ones words) with one bit test on plane s.  The collected
+// records are the set bits of plane B strictly between the two records: a match's length is K plus their
+// popcounts, and its rows enumerate them from the plane's words.  The walk is a loop of its own, so that the
+// kernels above keep their code.
+namespace {
+
+struct FollowManyMaps {
+  FollowMaps M;
+  uint32_t many;                  // bit s: slot s is a oneOrMore stage
+};
+
+// the first zero bit of the plane at or after `from` and before `limit` (<= n); none: limit
+__device__ __forceinline__ int64_t next_zero(const u64* __restrict__ plane, int64_t from, int64_t limit) {
+  if (from >= limit) return limit;
+  int64_t w = from >> 6;
+  const int64_t wl = (limit - 1) >> 6;             // (the last word read: limit <= n, inside the plane)
+  u64 x = ~plane[w] & (~0ull << (from & 63));
+  while (!x) {
+    if (++w > wl) return limit;
+    x = ~plane[w];
+  }
+  const int64_t q = w * 64 + __builtin_ctzll(x);
+  return q < limit ? q : limit;
+}
+
+// the set bits of the plane in [lo, hi), hi <= n; tiles without a set bit are passed by their second-level word
+__device__ __forceinline__ int64_t count_set(const u64* __restrict__ plane, const u64* __restrict__ sum, int64_t lo,
+                                             int64_t hi) {
+  if (lo >= hi) return 0;
+  const int64_t w0 = lo >> 6, w1 = (hi - 1) >> 6;
+  const u64 m0 = ~0ull << (lo & 63), m1 = ~0ull >> (63 - ((hi - 1) & 63));
+  if (w0 == w1) return __popcll(plane[w0] & m0 & m1);
+  int64_t c = __popcll(plane[w0] & m0) + __popcll(plane[w1] & m1);
+  for (int64_t w = w0 + 1; w < w1;) {
+    if ((w & 63) == 0 && w + 64 <= w1 && sum[w >> 6] == 0) {
+      w += 64;
+      continue;
+    }
+    c += __popcll(plane[w]);
+    w++;
+  }
+  return c;
+}
+
+// the hop out of many slot s - 1 at record p into slot s within the key segment ending at `end`: the record
+// taken, or -1 (the walk dies, or reaches the segment's end)
+__device__ __forceinline__ int64_t many_hop(const FollowMaps& M, int s, int64_t p, int64_t end) {
+  const u64* plane = M.bits + s * M.wpl;
+  if ((M.next >> s | M.next >> (s - 1)) & 1) {
+    const int64_t q = next_set(plane, M.sum + s * M.nt, p + 1, end);
+    return q < end ? q : -1;
+  }
+  const int64_t q = next_zero(M.bits + (s - 1) * M.wpl, p + 1, end);
+  return q < end && (plane[q >> 6] >> (q & 63) & 1) ? q : -1;
+}
+
+// the walk from start j0: its last record or -1; *len (or null): its entries, K + the collected records
+__device__ __forceinline__ int64_t many_walk(const FollowManyMaps& F, int64_t j0, int64_t* len) {
+  const FollowMaps& M = F.M;
+  const int64_t end = segment_end(M, j0);
+  int64_t p = j0, L = M.k;
+  for (int s = 1; s < M.k; s++) {
+    const u64* plane = M.bits + s * M.wpl;
+    if (F.many >> (s - 1) & 1) {
+      const int64_t q = many_hop(M, s, p, end);
+      if (q < 0) return -1;
+      if (len) {
+        const bool both_strict = !((M.next >> s | M.next >> (s - 1)) & 1);   // (then every record between is one)
+        L += both_strict ? q - p - 1 : count_set(M.bits + (s - 1) * M.wpl, M.sum + (s - 1) * M.nt, p + 1, q);
+      }
+      p = q;
+      continue;
+    }
+    p++;
+    if (M.next >> s & 1) {
+      p = next_set(plane, M.sum + s * M.nt, p, end);
+      if (p >= end) return -1;
+    } else if (p >= end || !(plane[p >> 6] >> (p & 63) & 1)) {
+      return -1;
+    }
+  }
+  if (len) *len = L;
+  return p;
+}
+
+// follow_walks for such a pattern; the count pass also sums the completed walks' lengths per word (wlen)
+template <bool WRITE>
+__global__ __launch_bounds__(256) void follow_many_walks(FollowManyMaps F, const int64_t* __restrict__ tile_starts,
+                                                        int64_t* __restrict__ wcnt, int64_t* __restrict__ wlen,
+                                                        const int64_t* __restrict__ wpre, u64* __restrict__ keys,
+                                                        u64* __restrict__ max_span) {
+  const FollowMaps& M = F.M;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t tile = blockIdx.x;
+  if (tile_starts[tile] == 0) {                    // uniform
+    if (!WRITE && threadIdx.x < 64) {
+      wcnt[tile * 64 + threadIdx.x] = 0;
+      wlen[tile * 64 + threadIdx.x] = 0;
+    }
+    return;
+  }
+  int64_t span = 0;
+  for (int i = 0; i < 16; i++) {
+    const int64_t w = tile * 64 + wid * 16 + i;
+    if (WRITE && wcnt[w] == 0) continue;           // uniform per wave
+    const u64 x = M.bits[w];
+    if (x == 0) {
+      if (!WRITE && lane == 0) {
+        wcnt[w] = 0;
+        wlen[w] = 0;
+      }
+      continue;
+    }
+    const int64_t j0 = w * 64 + lane;
+    int64_t e = -1, len = 0;
+    if (x >> lane & 1) e = many_walk(F, j0, WRITE ? nullptr : &len);
+    const u64 done = __ballot(e >= 0);
+    if (WRITE) {
+      if (e >= 0) keys[wpre[w] + __popcll(done & ((1ull << lane) - 1))] = (u64(e) << 31) | u64(j0);
+    } else {
+      if (e < 0) len = 0;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
+      if (lane == 0) {
+        wcnt[w] = __popcll(done);
+        wlen[w] = len;
+      }
+      if (e >= 0 && e - j0 > span) span = e - j0;
+    }
+  }
+  if (!WRITE) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int64_t o = __shfl_xor(span, d);
+      span = o > span ? o : span;
+    }
+    if (lane == 0 && u64(span) > *static_cast<volatile u64*>(max_span)) atomicMax(max_span, u64(span));
+  }
+}
+
+// the ordered matches' lengths
+__global__ __launch_bounds__(256) void follow_many_len(FollowManyMaps F, const u64* __restrict__ sorted, int64_t nm,
+                                                      int64_t* __restrict__ len) {
+  const int64_t m = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (m >= nm) return;
+  int64_t L = 0;
+  const int64_t e = many_walk(F, int64_t(sorted[m] & 0x7FFFFFFFull), &L);
+  len[m] = e >= 0 ? L : 0;
+}
+
+// The CSR of the ordered matches, a lane per match: batch indices, entries final slot first, a many slot's
+// collected records (descending) before the slot's own.  The walk runs forward, so its f-th record goes to
+// entry off + L - 1 - f; a store past the length the scan was given is dropped.
+__global__ __launch_bounds__(256) void follow_many_rows(FollowManyMaps F, const int32_t* __restrict__ key,
+                                                       const StencilProgram* __restrict__ P,
+                                                       const u64* __restrict__ sorted, int64_t nm,
+                                                       const int64_t* __restrict__ len, int64_t* __restrict__ match_record,
+                                                       int32_t* __restrict__ match_key, const int64_t* __restrict__ ent_off,
+                                                       int32_t* __restrict__ ent_name, int64_t* __restrict__ ent_record,
+                                                       int64_t* __restrict__ total) {
+  const int64_t m = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (m == 0) *total = nm;
+  if (m >= nm) return;
+  const FollowMaps& M = F.M;
+  const u64 v = sorted[m];
+  const int64_t j0 = int64_t(v & 0x7FFFFFFFull);
+  const int64_t L = len[m], top = ent_off[m] + L - 1;
+  const int64_t end = segment_end(M, j0);
+  match_record[m] = int64_t(v >> 31);
+  match_key[m] = key[j0];
+  int64_t f = 0, p = j0;
+  auto put = [&](int s, int64_t r) {
+    if (f < L) {
+      ent_record[top - f] = r;
+      ent_name[top - f] = P->name[s];
+    }
+    f++;
+  };
+  put(0, j0);
+  for (int s = 1; s < M.k; s++) {
+    const u64* plane = M.bits + s * M.wpl;
+    if (F.many >> (s - 1) & 1) {
+      const int64_t q = many_hop(M, s, p, end);
+      if (q < 0) return;                           // (not a completed walk: never among the sorted)
+      // the collected records: the set bits of plane s - 1 in (p, q), ascending
+      const u64* prev = M.bits + (s - 1) * M.wpl;
+      const u64* psum = M.sum + (s - 1) * M.nt;
+      if (p + 1 < q) {
+        const int64_t w0 = (p + 1) >> 6, w1 = (q - 1) >> 6;
+        for (int64_t w = w0; w <= w1;) {
+          if (w > w0 && (w & 63) == 0 && w + 64 <= w1 && psum[w >> 6] == 0) {
+            w += 64;
+            continue;
+          }
+          u64 x = prev[w];
+          if (w == w0) x &= ~0ull << ((p + 1) & 63);
+          if (w == w1) x &= ~0ull >> (63 - ((q - 1) & 63));
+          while (x) {
+            put(s - 1, w * 64 + __builtin_ctzll(x));
+            x &= x - 1;
+          }
+          w++;
+        }
+      }
+      p = q;
+    } else {
+      p++;
+      if (M.next >> s & 1) {
+        p = next_set(plane, M.sum + s * M.nt, p, end);
+        if (p >= end) return;
+      } else if (p >= end || !(plane[p >> 6] >> (p & 63) & 1)) {
+        return;
+      }
+    }
+    put(s, p);
+  }
+}
+
+}  // namespace
+
+hipError_t follow_many_count_launch(const FollowArgs& A, hipStream_t st) {
+  const int64_t nt = follow_tiles(A.n);
+  hipError_t e = hipMemsetAsync(A.max_span, 0, 8, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((follow_many_walks<false>), dim3(unsigned(nt)), dim3(256), 0, st,
+                     FollowManyMaps{follow_maps(A), A.many_mask}, A.tile_starts, A.wcnt, A.wlen, A.wpre, A.keys, A.max_span);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return exclusive_scan_pair(A.wcnt, A.wlen, nt * 64, nullptr, A.wpre, A.wlpre, A.nm, A.ne, A.scan_tmp, st);
+}
+
+hipError_t follow_many_write_launch(const FollowArgs& A, hipStream_t st) {
+  hipLaunchKernelGGL((follow_many_walks<true>), dim3(unsigned(follow_tiles(A.n))), dim3(256), 0, st,
+                     FollowManyMaps{follow_maps(A), A.many_mask}, A.tile_starts, A.wcnt, A.wlen, A.wpre, A.keys, A.max_span);
+  return hipGetLastError();
+}
+
+hipError_t follow_many_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int64_t* len,
+                                   int64_t* len_total, int64_t* match_record, int32_t* match_key, int64_t* ent_off,
+                                   int32_t* ent_name, int64_t* ent_record, int64_t* total, hipStream_t st) {
+  const FollowManyMaps F{follow_maps(A), A.many_mask};
+  if (nm > 0) {
+    hipLaunchKernelGGL(follow_many_len, dim3(blocks256(nm)), dim3(256), 0, st, F, sorted, nm, len);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = exclusive_scan(len, nm, ent_off, len_total, A.scan_tmp, st)) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(follow_many_rows, dim3(blocks256(nm)), dim3(256), 0, st, F, A.key, A.prog_dev, sorted, nm, len,
+                     match_record, match_key, ent_off, ent_name, ent_record, total);
   return hipGetLastError();
 }
 

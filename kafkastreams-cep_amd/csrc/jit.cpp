@@ -525,12 +525,14 @@ bool jit_check_masks(const Program& P, std::string& why) {
 
 // The follow path's evaluated form (follow_bits_dev.h): the same table, every group of a thread's tile loaded
 // before the first is evaluated, around follow_eval_bits' body.
-std::string jit_source_follow_bits(const Program& P, std::string& why) {
-  if (!P.follow_mask_ok) { why = "the follow path's evaluated form does not apply: " + P.follow_mask_why; return ""; }
+// many: of a pattern with oneOrMore stages in that form (Program::follow_many_prog)
+std::string jit_source_follow_bits(const Program& P, std::string& why, bool many) {
+  if (!many && !P.follow_mask_ok) { why = "the follow path's evaluated form does not apply: " + P.follow_mask_why; return ""; }
+  if (many && !(P.follow_many_ok && P.follow_many_eval)) { why = "the pattern has no evaluated form with oneOrMore stages"; return ""; }
   // groups of a thread's four loaded before the first evaluation: all four while their 16-B loads (4 VGPRs
   // each: the key, a column or metadata array of 4 B once, of 8 B twice) stay within 96 VGPRs, which leaves
   // the kernel four waves per SIMD; else two
-  const MaskProgram& m = P.follow_mask_prog;
+  const MaskProgram& m = many ? P.follow_many_prog : P.follow_mask_prog;
   int loads = 1;
   for (int c = 0; c < m.ncols; c++)
     if (m.used >> c & 1) loads += m.coltype[c] == T_I32 ? 1 : 2;
@@ -548,8 +550,8 @@ extern "C" __global__ __launch_bounds__(kcep::FB_THREADS) void kcep_follow_bits(
 )", why);
 }
 
-std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why) {
-  const std::string src = jit_source_follow_bits(P, why);
+std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why, bool many) {
+  const std::string src = jit_source_follow_bits(P, why, many);
   if (src.empty()) return nullptr;
   static const char* const names[] = {"kcep_follow_bits"};
   static hipFunction_t JitModule::* const slots[] = {&JitModule::follow_bits};
@@ -557,7 +559,7 @@ std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& 
 }
 
 bool jit_check_follow_bits(const Program& P, std::string& why) {
-  const std::string src = jit_source_follow_bits(P, why);
+  const std::string src = jit_source_follow_bits(P, why, !P.follow_mask_ok && P.follow_many_ok && P.follow_many_eval);
   std::vector<char> code;
   return !src.empty() && compile(src, code, why);
 }

@@ -48,8 +48,9 @@ std::shared_ptr<const JitModule> jit_masks(const Program& P, std::string& why, b
 bool jit_check_masks(const Program& P, std::string& why);
 
 // the same for the streaming kernel of the follow path's evaluated form (follow_bits_dev.h)
-std::string jit_source_follow_bits(const Program& P, std::string& why);
-std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why);
+// (many: of Program::follow_many_prog, a CEP_SESSION_FOLLOW_MANY session's)
+std::string jit_source_follow_bits(const Program& P, std::string& why, bool many = false);
+std::shared_ptr<const JitModule> jit_follow_bits(const Program& P, std::string& why, bool many = false);
 bool jit_check_follow_bits(const Program& P, std::string& why);
 
 }  // namespace kcep

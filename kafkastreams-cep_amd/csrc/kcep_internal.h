@@ -147,6 +147,16 @@ struct Program {
   StencilProgram follow_mask{};
   MaskProgram follow_mask_prog{};
   uint32_t follow_mask_next = 0;
+  // follow form with oneOrMore stages (compile.cpp analyse_follow_many; CEP_SESSION_FOLLOW_MANY sessions): the
+  // follow shape with oneOrMore stages between the first and the last, each provably exclusive of its
+  // successor -- a oneOrMore stage is one slot, bit s of follow_many_mask: slot s is one (a match holds every
+  // record of the slot's plane between the slot's record and the next slot's).  follow_many: the slots lowered
+  // directly, or (follow_many_eval) the program of the evaluated form with its bytecode in follow_many_prog
+  bool follow_many_ok = false, follow_many_eval = false;
+  std::string follow_many_why;
+  StencilProgram follow_many{};
+  MaskProgram follow_many_prog{};
+  uint32_t follow_many_next = 0, follow_many_mask = 0;
 };
 
 // ---- carried state of the stencil / chain paths (CEP_SESSION_CARRY) ----

@@ -218,6 +218,12 @@ struct FollowArgs {
   int64_t* wopen;
   int64_t* wopre;
   int64_t* nopen;                   // device: open in-batch walks
+  // CEP_SESSION_FOLLOW_MANY sessions: bit s of many_mask: slot s is a oneOrMore stage (Program::follow_many_mask);
+  // the completed walks' entries per word of slot 0's bitmap (64 t words), their prefix, their sum
+  uint32_t many_mask = 0;
+  int64_t* wlen = nullptr;
+  int64_t* wlpre = nullptr;
+  int64_t* ne = nullptr;            // device: entries of the completed walks (K + the collected records each)
 };
 // The carried walks of a follow carry session (follow.hip): a walk is k int64 words -- slots taken s, the
 // stream positions of its s records, zeros -- in the runs path's tail pool (rtab: offset and count per key,
@@ -266,6 +272,16 @@ hipError_t follow_count_launch(const FollowArgs& A, hipStream_t st);
 hipError_t follow_write_launch(const FollowArgs& A, hipStream_t st);
 hipError_t follow_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int32_t* out,
                               int64_t* total, hipStream_t st);
+
+// CEP_SESSION_FOLLOW_MANY (follow.hip "oneOrMore slots"): the count pass, which also sums the walks' lengths
+// (A.wlen, A.wlpre, A.ne; scan_tmp: t / 8 + 2 words); the write pass; then per ordered match its length (len),
+// their prefix (ent_off; *len_total their sum; scan_tmp: nm / 1024 + 1 words) and the runs path's CSR with batch
+// indices as positions, *total = nm
+hipError_t follow_many_count_launch(const FollowArgs& A, hipStream_t st);
+hipError_t follow_many_write_launch(const FollowArgs& A, hipStream_t st);
+hipError_t follow_many_rows_launch(const FollowArgs& A, const unsigned long long* sorted, int64_t nm, int64_t* len,
+                                   int64_t* len_total, int64_t* match_record, int32_t* match_key, int64_t* ent_off,
+                                   int32_t* ent_name, int64_t* ent_record, int64_t* total, hipStream_t st);
 
 // ---- masks.hip: the mask pre-pass of CEP_SESSION_MASK_PASS sessions (jf: the per-pattern kernel, or null) ----
 hipError_t masks_launch(const MaskArgs& A, hipStream_t st, hipFunction_t jf);

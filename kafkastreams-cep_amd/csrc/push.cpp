@@ -711,6 +711,56 @@ static int push_follow_carry(cep_session* s, FollowArgs& A, const MaskArgs& M, h
   return CEP_OK;
 }
 
+// A batch of a pattern with oneOrMore stages (CEP_SESSION_FOLLOW_MANY, follow.hip "oneOrMore slots"): the same
+// planes, the walks counted with their lengths; the one host synchronisation yields matches, entries and the
+// longest span; then the write pass and the ordering of every follow batch, and the runs path's CSR -- batch
+// indices as positions, the device match count at scal[3] -- instead of K-int rows.
+static int push_follow_many(cep_session* s, FollowArgs& A, const MaskArgs& M, hipStream_t st) {
+  const int64_t n = A.n, nt = follow_tiles(n);
+  if (s->scan_tmp.ensure(size_t(std::max(nt / 8, n / 1024) + 4) * 8)) return fail(CEP_E_HIP, "allocation failed");
+  int64_t* scal = s->scal.as<int64_t>();
+  A.scan_tmp = s->scan_tmp.as<int64_t>();
+  A.many_mask = s->follow_many_mask;
+  A.wlen = s->fw_len.as<int64_t>();
+  A.wlpre = s->fw_lpre.as<int64_t>();
+  A.ne = scal + 6;
+  HIPCHECK(follow_planes_launch(s, A, M, st));
+  HIPCHECK(follow_many_count_launch(A, st));
+  // the batch's one host synchronisation: the completed walks, their longest span, their entries
+  int64_t h[3] = {0, 0, 0};
+  HIPCHECK(hipMemcpyAsync(h, scal + 4, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  const int64_t nm = h[0], span = h[1], ne = h[2];
+  if (nm < 0 || nm > n) return fail(CEP_E_RUN_CAPACITY, "more completed walks than records");
+  if (ne < nm * A.k || ne >= (int64_t(1) << 31)) return fail(CEP_E_RUN_CAPACITY, "a follow batch's matches hold 2^31 entries or more");
+  const size_t nmb = size_t(std::max<int64_t>(nm, 1)), neb = size_t(std::max<int64_t>(ne, 1));
+  if (nm > 0) {
+    int bits = 1;                                  // bits of the completing record
+    while ((int64_t(1) << bits) <= n) bits++;
+    const bool ranked = span <= 1024 && !getenv_flag("KCEP_RUNS_RADIX");
+    size_t tmp_bytes = 0;
+    if (!ranked) HIPCHECK(runs_sort(nullptr, nullptr, nm, bits, nullptr, &tmp_bytes, st));
+    if (s->rk.ensure(nmb * 8) || s->rk_sorted.ensure(nmb * 8) || s->r_len.ensure(nmb * 8) ||
+        (!ranked && s->rk_tmp.ensure(std::max<size_t>(tmp_bytes, 16))) || s->o_record.ensure(nmb * 8) ||
+        s->o_key.ensure(nmb * 4) || s->o_entoff.ensure(nmb * 8) || s->o_name.ensure(neb * 4) || s->o_entrec.ensure(neb * 8))
+      return fail(CEP_E_HIP, "allocation failed");
+    A.keys = s->rk.as<unsigned long long>();
+    HIPCHECK(follow_many_write_launch(A, st));
+    if (ranked)
+      HIPCHECK(runs_order_launch(A.keys, nm, int(span), s->rk_sorted.as<unsigned long long>(), s->r_len.as<int64_t>(), st));
+    else
+      HIPCHECK(runs_sort(A.keys, s->rk_sorted.as<unsigned long long>(), nm, bits, s->rk_tmp.p, &tmp_bytes, st));
+  }
+  // (r_len: the ordering's scratch, then the ordered matches' lengths; scal[7]: their sum, which is ne)
+  HIPCHECK(follow_many_rows_launch(A, s->rk_sorted.as<unsigned long long>(), nm, s->r_len.as<int64_t>(), scal + 7,
+                                   s->o_record.as<int64_t>(), s->o_key.as<int32_t>(), s->o_entoff.as<int64_t>(),
+                                   s->o_name.as<int32_t>(), s->o_entrec.as<int64_t>(), scal + 3, st));
+  s->g_matches = nm;
+  s->g_entries = ne;
+  if (s->timing) HIPCHECK(hipEventRecord(s->eb1, st));
+  return CEP_OK;
+}
+
 // Skip-till-next walks (follow.hip): the slots' bitmaps in one streaming pass, the completed walks counted
 // and compacted in start order, ordered by (completing record, start) as the runs path orders its runs, then
 // written as K-int rows -- from there the batch is a finished stencil batch without carry (cep_collect).
@@ -721,7 +771,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   int rc = stage_inputs(s, b, st, in, true);
   if (rc) return rc;
   s->d_key = in.key;
-  if (s->carry) reset_results(s);
+  if (s->carry || s->follow_many) reset_results(s);
   if (n == 0) {
     HIPCHECK(hipMemsetAsync(s->total.p, 0, 8, st));
     return push_empty(s, st, true);
@@ -732,7 +782,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   if (s->follow_eval) {
     // the evaluated form: the columns and metadata its predicates read -- the caller's, group_batch's or
     // filter_batch's, with their stream positions (a default ts / offset is the position)
-    const MaskProgram& MP = s->pat->prog.follow_mask_prog;
+    const MaskProgram& MP = s->follow_many ? s->pat->prog.follow_many_prog : s->pat->prog.follow_mask_prog;
     M.P = s->mprog.as<MaskProgram>();
     M.key = in.key;
     M.topic = (MP.meta & MASK_META_TOPIC) ? in.topic : nullptr;
@@ -782,6 +832,7 @@ int push_follow(cep_session* s, const cep_batch* b, hipStream_t st) {
   A.nm = scal + 4;
   A.max_span = reinterpret_cast<unsigned long long*>(scal + 5);
   if (s->carry) return push_follow_carry(s, A, M, st);
+  if (s->follow_many) return push_follow_many(s, A, M, st);
   HIPCHECK(follow_planes_launch(s, A, M, st));
   HIPCHECK(follow_count_launch(A, st));
   // the batch's one host synchronisation: the completed walks and their longest span

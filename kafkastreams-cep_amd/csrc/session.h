@@ -114,6 +114,11 @@ struct cep_session {
   // follow_split (KCEP_FOLLOW_MASK_SPLIT=1 at open): from the pre-pass into mcol and follow_bits over it
   bool follow_eval = false, follow_split = false;
   uint32_t follow_next = 0;     // a follow session's skip-till-next slots
+  // a follow session of a pattern with oneOrMore stages (Program::follow_many_ok, CEP_SESSION_FOLLOW_MANY):
+  // sp = &follow_many, its batches leave the runs path's CSR (variable-length matches); follow_many_mask: its
+  // oneOrMore slots
+  bool follow_many = false;
+  uint32_t follow_many_mask = 0;
   int last_path = 0;            // path of the last batch
   int device = 0;
   hipStream_t stream = nullptr;
@@ -134,6 +139,9 @@ struct cep_session {
   // records of k words): the open starts' plane, their count per word and its prefix; the continuations per
   // (segment, slot); per carried walk of the batch's keys its outcome flags, their prefixes, the completed ones
   DBuf fw_open, fw_ocnt, fw_opre, fw_res, fw_cdone, fw_copen, fw_cdpre, fw_copre, fw_cdx;
+  // ... of a pattern with oneOrMore stages (CEP_SESSION_FOLLOW_MANY): the completed walks' entries per word and
+  // their prefix
+  DBuf fw_len, fw_lpre;
   // ---- staging of host-resident batches (stage_host): a pinned ring the caller's columns are copied
   // into in chunks, each chunk moved by one async copy into one packed device image; caller memory
   // that is itself pinned is copied from directly and the push waits for that copy ----
@@ -281,7 +289,8 @@ inline int tail_rw(const cep_session* s) {
 inline bool tail_session(const cep_session* s) { return s->carry && (s->path == CEP_PATH_RUNS || s->path == CEP_PATH_FOLLOW); }
 // the last batch left the general / runs CSR on the device (o_record ...; its match count in scal[3])
 inline bool csr_batch(const cep_session* s) {
-  return s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS || (s->last_path == CEP_PATH_FOLLOW && s->carry);
+  return s->last_path == CEP_PATH_GENERAL || s->last_path == CEP_PATH_RUNS ||
+         (s->last_path == CEP_PATH_FOLLOW && (s->carry || s->follow_many));
 }
 inline bool halo_session(const cep_session* s) { return s->carry && (s->path == CEP_PATH_STENCIL || s->path == CEP_PATH_CHAIN); }
 

@@ -40,6 +40,7 @@ SESSION_WAVE_NFA = 16
 SESSION_MASK_PASS = 32     # opt-in: stencil / chain path for eligible multi-column predicates (CompiledPattern.mask_pass)
 SESSION_FOLLOW = 64        # opt-in: the follow path for eligible skip-till-next patterns (CompiledPattern.follow)
 SESSION_FOLLOW_CARRY = 128  # ... on carry sessions too: the waiting walks carried per key (implies SESSION_FOLLOW)
+SESSION_FOLLOW_MANY = 256  # ... also patterns with oneOrMore stages (CompiledPattern.follow_many; implies SESSION_FOLLOW)
 
 
 class CepError(RuntimeError):
@@ -87,7 +88,7 @@ SYMBOLS = ["cep_compile", "cep_pattern_free", "cep_pattern_get_info", "cep_patte
            "cep_session_set_max_key_words", "cep_state_to_reference", "cep_pattern_check", "cep_batch_attempts",
            "cep_csr_check", "cep_batch_id", "cep_batch_ready", "cep_collect_batch", "cep_batch_stopped",
            "cep_filter_tile_records", "cep_pattern_mask_pass", "cep_pattern_follow", "cep_follow_tile_records",
-           "cep_pattern_follow_mask"]
+           "cep_pattern_follow_mask", "cep_pattern_follow_many"]
 
 _lib = None
 
@@ -158,6 +159,9 @@ def lib():
         L.cep_follow_tile_records.restype = C.c_int32
     if hasattr(L, "cep_pattern_follow_mask"):   # (KCEP_LIB A/B runs may load an older build)
         L.cep_pattern_follow_mask.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "cep_pattern_follow_many"):   # (KCEP_LIB A/B runs may load an older build)
+        L.cep_pattern_follow_many.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_int32)]
     L.cep_key_profile.argtypes = [P, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cep_pattern_kernel_source.argtypes = [P, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cep_pattern_build_kernels.argtypes = [P, C.c_int32]
@@ -276,6 +280,19 @@ class CompiledPattern:
             return True, k.value, nxt.value, ""
         return False, 0, 0, lib().cep_last_error().decode()
 
+    @property
+    def follow_many(self):
+        """cep_pattern_follow_many: ``(ok, k, next_mask, many_mask, evaluated, why)`` -- whether a
+        ``follow_many=True`` session runs the pattern, which has ``oneOrMore`` stages, on the follow path; its
+        slots (a ``oneOrMore`` stage is one), the masks of the skip-till-next and of the ``oneOrMore`` slots,
+        whether it needs the evaluated form (then the session needs ``mask_pass=True`` too), and the reason when
+        it does not."""
+        k, nxt, many, ev = C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        rc = lib().cep_pattern_follow_many(self.h, C.byref(k), C.byref(nxt), C.byref(many), C.byref(ev))
+        if rc == CEP_OK:
+            return True, k.value, nxt.value, many.value, bool(ev.value), ""
+        return False, 0, 0, 0, False, lib().cep_last_error().decode()
+
     def kernel_source(self, path=PATH_RUNS) -> str:
         """HIP source of the kernels compiled for this pattern (cep_pattern_kernel_source)."""
         n = C.c_size_t()
@@ -305,7 +322,7 @@ class Session:
 
     def __init__(self, pattern: CompiledPattern, max_events: int, mode=MODE_PROCESSOR, device=0, force_path=0,
                  carry=False, max_keys=0, interpret=False, profile=False, max_key_words=0, lane_nfa=None,
-                 max_pool_bytes=0, mask_pass=False, follow=False, follow_carry=False):
+                 max_pool_bytes=0, mask_pass=False, follow=False, follow_carry=False, follow_many=False):
         """``carry=True``: every key's NFA state continues across batches (CEP_SESSION_CARRY);
         key ids must then be dense in [0, max_keys) and record positions are stream positions.
         ``interpret=True``: the built-in interpreting kernels instead of kernels compiled for the
@@ -325,14 +342,19 @@ class Session:
         in its evaluated form, a pattern of that shape whose predicates read several columns, arithmetic or
         event metadata (``CompiledPattern.follow_mask``): its streaming kernel evaluates them into the
         bitmaps, compiled for the pattern unless ``interpret=True``.  With one of the two alone such a pattern
-        opens where it always did."""
+        opens where it always did.
+        ``follow_many=True`` (CEP_SESSION_FOLLOW_MANY): the follow path also takes a pattern with ``oneOrMore``
+        stages between its first and last (``CompiledPattern.follow_many``), such as A followedBy B+
+        followedBy C; its matches have variable length.  Implies ``follow=True``; no effect with ``carry=True``;
+        a pattern that needs the evaluated form is taken only with ``mask_pass=True`` too."""
         self.pattern = pattern
         self.h = C.c_void_p()
         # lane_nfa: None = the library's choice, True = one key per lane, False = one key per wave
         flags = ((SESSION_CARRY if carry else 0) | (SESSION_INTERPRET if interpret else 0) |
                  (SESSION_PROFILE if profile else 0) | (SESSION_LANE_NFA if lane_nfa else 0) |
                  (SESSION_WAVE_NFA if lane_nfa is False else 0) | (SESSION_MASK_PASS if mask_pass else 0) |
-                 (SESSION_FOLLOW if follow else 0) | (SESSION_FOLLOW_CARRY if follow_carry else 0))
+                 (SESSION_FOLLOW if follow else 0) | (SESSION_FOLLOW_CARRY if follow_carry else 0) |
+                 (SESSION_FOLLOW_MANY if follow_many else 0))
         o = Opts(device, mode, force_path, flags, max_events, max_keys, 0.0, max_key_words, max_pool_bytes)
         check(lib().cep_session_open(pattern.h, C.byref(o), C.byref(self.h)))
         self.path = lib().cep_session_path(self.h)
